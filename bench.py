@@ -7,11 +7,20 @@ decoder, bpp + masked MSE) of a synthetic 256x256 RGBA batch of 8 per GPU
 N > 1: one process per GPU (torchrun), independent replicas (inference has no
 exchange step), barrier + synchronize around the timed region, MAX over ranks.
 
-Rank 0 also prints, in the same JSON line:
+A plain run sets up, warms up, times ``--steps`` steps and prints one JSON line
+(metric, value, unit, ms_per_step, ...).  ``--dump-outputs DIR`` also writes what
+the last timed step computed as DIR/<name>.npy (same arguments -> same inputs).
+
+With ``--full`` rank 0 also measures and prints, in the same JSON line:
+  parity_mode   -- the same config timed in fp32;
+  dp_train      -- the data-parallel training step (BASELINE config 5);
   roofline      -- the dominant kernel's algorithmic FLOP/s (HIP events on the
                    launching stream, eager attribution pass) vs its peak;
   cpu_baseline  -- the CPU oracle (fp32 PyTorch restatement of the reference)
-                   on a bounded sample of the same workload, on this host.
+                   on a bounded sample of the same workload, on this host;
+  parity        -- bpp / PSNR / MS-SSIM and symbol accounting vs that oracle.
+The other workloads (--train, --rgba, --alpha, --codec) keep their CPU baselines,
+attribution passes and parity checks behind ``--full`` in the same way.
 """
 import argparse
 import json
@@ -50,6 +59,46 @@ def synth_inputs(B, H, W, seed=0):
         elif k == 3:
             a[b].zero_()
     return torch.where(a > 0, rgb, a), a
+
+
+DUMP_BUDGET = 60 * 1000 * 1000     # array bytes of one --dump-outputs (files: under 64 MB)
+OUT_NAMES = ("x_hat", "mse", "bpp", "y_bpp", "z_bpp")   # the codecs' forward 5-tuple
+
+
+class KeepLast:
+    """An eager (--no-graph) step that keeps its latest return value for --dump-outputs; a
+    graph replay needs none: the captured step's output tensors hold the last replay's."""
+    def __init__(self, step):
+        self.step, self.out = step, None
+
+    def __call__(self):
+        self.out = self.step()
+        return self.out
+
+
+def dump_outputs(path, named, rank=0):
+    """--dump-outputs: write each (name, tensor) of ``named`` -- what the timed path returned
+    in its last step -- as <path>/<name>.npy (ranks > 0: <name>.rank<r>.npy), float32 (float64
+    kept).  All arrays together stay under DUMP_BUDGET: an array larger than its share (of
+    what the smaller ones left) is replaced by a fixed sample of its flattened elements
+    (sorted indices from numpy.random.default_rng(0)), the same elements on every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = []
+    for name, t in named:
+        t = torch.as_tensor(t).detach()
+        arrs.append((name, t.to("cpu", torch.float64 if t.dtype == torch.float64
+                                else torch.float32).numpy()))
+    left = DUMP_BUDGET
+    for i, (name, arr) in enumerate(sorted(arrs, key=lambda na: na[1].nbytes)):
+        share = left // (len(arrs) - i)      # smallest first: what they leave goes to the rest
+        if arr.nbytes > share:
+            keep = share // arr.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(arr.size, size=keep, replace=False))
+            arr = arr.reshape(-1)[idx]
+        left -= arr.nbytes
+        fn = f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"
+        np.save(os.path.join(path, fn), arr)
 
 
 # Attribution runs enqueue one eager step behind a GPU spin (torch.cuda._sleep, in clock
@@ -377,23 +426,27 @@ def main_train(args, world, rank, dev, dist):
     ms = elapsed / args.steps * 1e3
     value = world * B * S * S * args.steps / elapsed / 1e6
     loss_val = out.item()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("loss", out)], rank)
     del out, run
     if graph is not None:
         del gout, graph                       # the captured graph's autograd nodes
     if rank == 0:
-        prof = rt.LaunchProfiler()
-        rt.PROFILER = prof
-        for _ in range(2):
-            torch.cuda._sleep(SPIN_TRAIN)   # queue the whole step behind a spin: GPU-side times
-            step()
-        rt.PROFILER = None
-        summ = prof.summary()
-        if args.layers:
-            write_layers(prof, args.layers, 2)
-        traffic_file = args.traffic_file
-        if traffic_file is None:
-            traffic_file = latest_profile("pmc_traffic_train.json")
-        roof, total_ms = roofline_of(summ, args.dtype, 2, traffic_file)
+        roof = summ = None
+        if args.attribution:
+            prof = rt.LaunchProfiler()
+            rt.PROFILER = prof
+            for _ in range(2):
+                torch.cuda._sleep(SPIN_TRAIN)   # queue the whole step behind a spin: GPU-side times
+                step()
+            rt.PROFILER = None
+            summ = prof.summary()
+            if args.layers:
+                write_layers(prof, args.layers, 2)
+            traffic_file = args.traffic_file
+            if traffic_file is None:
+                traffic_file = latest_profile("pmc_traffic_train.json")
+            roof, total_ms = roofline_of(summ, args.dtype, 2, traffic_file)
         rec = {"metric": TRAIN_METRIC, "value": round(value, 2), "unit": "MPix/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
@@ -676,6 +729,8 @@ def main_codec(args, dev):
     tc.sort()
     td.sort()
     mc, md = tc[len(tc) // 2], td[len(td) // 2]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("x_hat", rec["x_hat"])])
     nbytes = sum(len(s) for s in out["strings"][0]) + sum(len(s) for s in out["strings"][1])
     _, me = mask_pyramid(a, 4)
     with torch.no_grad():
@@ -764,15 +819,20 @@ def main_rgba(args, dev):
     el = time.perf_counter() - t0
     if args.no_graph:
         out = step()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, list(zip(
+            ("recon_image", "recon_mask", "mse", "bpp", "psnr"), out[:5])))
     # eval metric of the same loop (trainRGB.py:311), outside the timed codec region as there
     from rgbac.metrics.ms_ssim_torch import ms_ssim
     msv = ms_ssim(x, out[0], data_range=1.0).item()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(10):
-        ms_ssim(x, out[0], data_range=1.0)
-    torch.cuda.synchronize()
-    ms_ms = (time.perf_counter() - t0) / 10 * 1e3
+    ms_ms = None
+    if args.full:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(10):
+            ms_ssim(x, out[0], data_range=1.0)
+        torch.cuda.synchronize()
+        ms_ms = round((time.perf_counter() - t0) / 10 * 1e3, 3)
     npx = B * S * S
     rec = {"metric": "MPixels/sec RGBA encode+decode (alpha codec -> constraint -> RGB codec)",
            "value": round(npx * args.steps / el / 1e6, 3), "unit": "MPix/s", "n_gpus": 1,
@@ -783,7 +843,7 @@ def main_rgba(args, dev):
            "config": {"workload": f"RGBA eval pipeline trainRGB.py:282-306, {S}x{S}",
                       "batch": B, "hip_graph": not args.no_graph},
            "bpp": round(out[3].item(), 5), "psnr": round(out[4].item(), 4),
-           "ms_ssim": round(msv, 6), "ms_ssim_ms_per_batch": round(ms_ms, 3),
+           "ms_ssim": round(msv, 6), "ms_ssim_ms_per_batch": ms_ms,
            "cpu_baseline": None}
     if not args.no_cpu_baseline:
         rec["cpu_baseline"] = cpu_baseline_rgba(args.cpu_seconds)
@@ -792,9 +852,10 @@ def main_rgba(args, dev):
 
 def main_alpha(args, dev):
     """--alpha: BASELINE config 1 -- AutoEncoderMask_Journal encode+decode of one 256x256 alpha
-    tile (trainmask.py:242-293, config4096.json), HIP graph replay, in the bench dtype and in
-    fp32; cpu_baseline = the oracle's mask_forward on the same tile (the reference runs this
-    config on PyTorch CPU); parity (fp32, teacher-forced symbol accounting) vs the oracle."""
+    tile (trainmask.py:242-293, config4096.json), HIP graph replay, in the bench dtype.  With
+    --full also: the same in fp32; cpu_baseline = the oracle's mask_forward on the same tile
+    (the reference runs this config on PyTorch CPU); parity (fp32, teacher-forced symbol
+    accounting) vs the oracle."""
     from oracle import parity as opar
     from oracle import ref_model as ref
     from rgbac import runtime as rt
@@ -806,7 +867,8 @@ def main_alpha(args, dev):
     sd = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
     ad = a.to(dev)
     res = {}
-    for dtn in ([args.dtype, "f32"] if args.dtype != "f32" else ["f32"]):
+    dtypes = [args.dtype] + (["f32"] if args.full and args.dtype != "f32" else [])
+    for dtn in dtypes:
         net.set_compute_dtype(torch.bfloat16 if dtn == "bf16" else torch.float32)
 
         def step():
@@ -814,13 +876,31 @@ def main_alpha(args, dev):
                 return net(ad)
         step()
         torch.cuda.synchronize()
-        run, graph, _ = capture(step, args.no_graph)
+        run, graph, out = capture(step, args.no_graph)
+        if graph is None and args.dump_outputs:
+            run = KeepLast(step)
         for _ in range(args.warmup):
             run()
         el = time_steps(run, args.steps, None, dev)
         res[dtn] = {"value": round(B * S * S * args.steps / el / 1e6, 3),
                     "ms_per_step": round(el / args.steps * 1e3, 4)}
-        del run, graph
+        if args.dump_outputs and dtn == args.dtype:
+            out = out if graph is not None else run.out
+            dump_outputs(args.dump_outputs, list(zip(OUT_NAMES, out)))
+        del run, graph, out
+    main = res[args.dtype]
+    rec = {"metric": "MPixels/sec alpha-codec encode+decode (AutoEncoderMask_Journal), 256x256 tile",
+           "value": main["value"], "unit": "MPix/s", "n_gpus": 1, "steps": args.steps,
+           "warmup": args.warmup, "ms_per_step": main["ms_per_step"], "higher_is_better": True,
+           "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
+           "data": "synthetic (ramped-ellipse alpha k/255; random-init weights, torch seed 234, "
+                   "EncoderMask.7 x20 so latent symbols are non-zero)",
+           "config": {"workload": f"BASELINE config 1: AutoEncoderMask_Journal forward, {S}x{S}",
+                      "batch": B, "hip_graph": not args.no_graph},
+           "parity_mode": None, "parity": None, "cpu_baseline": None}
+    if not args.full:
+        print(json.dumps(rec), flush=True)
+        return
     # parity (fp32, one tile) and the CPU baseline
     net.set_compute_dtype(torch.float32)
     dbg = {}
@@ -838,15 +918,7 @@ def main_alpha(args, dev):
             if time.perf_counter() - t0 >= args.cpu_seconds or n >= 2000:
                 break
         dt_cpu = time.perf_counter() - t0
-    main = res[args.dtype]
-    rec = {"metric": "MPixels/sec alpha-codec encode+decode (AutoEncoderMask_Journal), 256x256 tile",
-           "value": main["value"], "unit": "MPix/s", "n_gpus": 1, "steps": args.steps,
-           "warmup": args.warmup, "ms_per_step": main["ms_per_step"], "higher_is_better": True,
-           "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
-           "data": "synthetic (ramped-ellipse alpha k/255; random-init weights, torch seed 234, "
-                   "EncoderMask.7 x20 so latent symbols are non-zero)",
-           "config": {"workload": f"BASELINE config 1: AutoEncoderMask_Journal forward, {S}x{S}",
-                      "batch": B, "hip_graph": not args.no_graph},
+    rec.update({
            "parity_mode": {"dtype": "f32", **res["f32"]},
            "parity": {"sample": f"the same tile, fp32, vs the CPU oracle",
                       "rel_d_bpp": float(f"{abs(dev_out[2] - r[2].item()) / r[2].item():.3g}"),
@@ -858,7 +930,7 @@ def main_alpha(args, dev):
            "cpu_baseline": {"value": round(n * S * S / dt_cpu / 1e6, 4), "unit": "MPix/s",
                             "cores": cores, "kind": "port",
                             "sample": f"oracle mask_forward fp32, the same {S}x{S} tile, {n} "
-                                      f"forwards, {dt_cpu:.1f} s, torch threads {cores}"}}
+                                      f"forwards, {dt_cpu:.1f} s, torch threads {cores}"}})
     print(json.dumps(rec), flush=True)
 
 
@@ -896,7 +968,17 @@ def main():
     ap.add_argument("--dp-warmup", type=int, default=3)
     ap.add_argument("--traffic-file", default=None,
                     help="PMC traffic summary (default: the committed profiles/ one)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: fp32 parity mode, "
+                         "dp_train, roofline attribution, CPU baseline, parity vs the oracle "
+                         "(each still switched off by its own --no-* option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy")
     args = ap.parse_args()
+    # the eager attribution pass (roofline, --kernels, --layers) takes steps of its own
+    args.attribution = args.full or args.kernels or args.layers is not None
+    if not args.full:
+        args.no_cpu_baseline = args.no_parity_mode = args.no_dp_train = True
     if args.train and args.batch == 8 and "--batch" not in sys.argv:
         args.batch = 16
 
@@ -1010,13 +1092,20 @@ def main_forward(args, world, rank, dev, dist):
     tuned = tune_cache_setup(args, os.path.join(ROOT, "profiles", f"tune_fwd_{args.dtype}_b{B}_{S}.json"))
     step()                                             # packs weights, warms caches (and tunes)
     torch.cuda.synchronize()
-    run, graph, _ = capture(step, args.no_graph)
+    run, graph, out = capture(step, args.no_graph)
+    if graph is None and args.dump_outputs:
+        run = KeepLast(step)
     for _ in range(args.warmup):
         run()
     torch.cuda.synchronize()
     elapsed = time_steps(run, args.steps, dist, dev)
     ms = elapsed / args.steps * 1e3
     value = world * B * S * S * args.steps / elapsed / 1e6
+    if args.dump_outputs:
+        # the captured step's output tensors hold the last replay's results
+        out = out if graph is not None else run.out
+        dump_outputs(args.dump_outputs, list(zip(OUT_NAMES, out)), rank)
+    del out
 
     # fp32 parity mode (the reference's own precision) on the same config, timed the same way
     parity_mode = None
@@ -1046,31 +1135,33 @@ def main_forward(args, world, rank, dev, dist):
         dp = dp_train_record(args, world, rank, dev, dist)
 
     if rank == 0:
-        # ---- roofline attribution: eager steps, each queued behind a GPU spin so the host has
-        # enqueued every launch before the GPU reaches them (back-to-back execution as in the
-        # graph replay), with a fence-free HIP event (rgbac_timer_*: no cache writeback /
-        # invalidate per record) on the launching stream around every launch.
-        prof = rt.LaunchProfiler()
-        nrep = 3
-        rt.PROFILER = prof
-        for _ in range(nrep):
-            torch.cuda._sleep(SPIN_FWD)
-            step()
-            torch.cuda.synchronize()
-        rt.PROFILER = None
-        summ = prof.summary()
-        if args.layers:
-            write_layers(prof, args.layers, nrep)
-        traffic_file = args.traffic_file
-        if traffic_file is None:                       # a summary taken on this workload
-            traffic_file = (latest_profile(f"pmc_traffic_fwd_b{B}_{S}.json") or
-                            latest_profile("pmc_traffic_fwd.json"))
-        roof, total_ms = roofline_of(summ, args.dtype, nrep, traffic_file,
-                                     {"batch": B, "size": S, "dtype": args.dtype})
-        roof["timing"] = "eager steps behind a GPU spin, fence-free HIP events per launch"
-        if roof["traffic"] is not None:
-            roof["traffic_source"] = os.path.relpath(traffic_file, ROOT)
-        fwd_flops = sum(d["flops"] for d in summ.values()) / nrep
+        roof = summ = fwd_flops = None
+        if args.attribution:
+            # ---- roofline attribution: eager steps, each queued behind a GPU spin so the host
+            # has enqueued every launch before the GPU reaches them (back-to-back execution as
+            # in the graph replay), with a fence-free HIP event (rgbac_timer_*: no cache
+            # writeback / invalidate per record) on the launching stream around every launch.
+            prof = rt.LaunchProfiler()
+            nrep = 3
+            rt.PROFILER = prof
+            for _ in range(nrep):
+                torch.cuda._sleep(SPIN_FWD)
+                step()
+                torch.cuda.synchronize()
+            rt.PROFILER = None
+            summ = prof.summary()
+            if args.layers:
+                write_layers(prof, args.layers, nrep)
+            traffic_file = args.traffic_file
+            if traffic_file is None:                       # a summary taken on this workload
+                traffic_file = (latest_profile(f"pmc_traffic_fwd_b{B}_{S}.json") or
+                                latest_profile("pmc_traffic_fwd.json"))
+            roof, total_ms = roofline_of(summ, args.dtype, nrep, traffic_file,
+                                         {"batch": B, "size": S, "dtype": args.dtype})
+            roof["timing"] = "eager steps behind a GPU spin, fence-free HIP events per launch"
+            if roof["traffic"] is not None:
+                roof["traffic_source"] = os.path.relpath(traffic_file, ROOT)
+            fwd_flops = sum(d["flops"] for d in summ.values()) / nrep
         rec = {"metric": METRIC, "value": round(value, 2), "unit": "MPix/s", "n_gpus": world,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -1083,7 +1174,7 @@ def main_forward(args, world, rank, dev, dist):
                           "parallelism": f"replicas{world}", "hip_graph": graph is not None,
                           "tile_cache": tuned and os.path.relpath(tuned, ROOT)},
                "roofline": roof,
-               "achieved_model_tflops": round(fwd_flops / (ms * 1e-3) / 1e12, 2),
+               "achieved_model_tflops": fwd_flops and round(fwd_flops / (ms * 1e-3) / 1e12, 2),
                "parity_mode": parity_mode, "dp_train": dp}
         if args.kernels:
             rec["kernels"] = {k: {"launches": v["launches"] // nrep, "ms": round(v["ms"] / nrep, 4),

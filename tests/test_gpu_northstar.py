@@ -285,3 +285,45 @@ def test_config2_bf16_headline_b8_256(device):
     assert rel_bpp < BF16_BAR["rel_d_bpp"]
     assert d_psnr < BF16_BAR["d_psnr_db"]
     assert max(d_ms) < BF16_BAR["d_ms_ssim"]
+
+
+def test_bench_plain_run_dumps_last_step_outputs(device, tmp_path):
+    """A plain ``bench.py --gpus 1 --steps N --warmup W --dump-outputs DIR`` run: one JSON
+    line whose ``steps`` is N and ``ms_per_step`` the time of one of them, none of the
+    ``--full`` measurements in it, and DIR/<name>.npy holding, in float32, exactly what the
+    timed path returns for the bench's inputs (the same step run here in this process)."""
+    import json
+    import subprocess
+
+    import numpy as np
+    from bench import OUT_NAMES, rgb_net, synth_inputs
+    from rgbac import runtime as rt
+    from rgbac.layers.SupplyMask import mask_pyramid
+    out_dir = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps",
+                        "3", "--warmup", "1", "--dump-outputs", str(out_dir)],
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["dtype"] == "bf16"
+    assert rec["unit"] == "MPix/s" and rec["higher_is_better"] is True
+    assert rec["ms_per_step"] > 0
+    assert abs(rec["value"] - 8 * 256 * 256 / (rec["ms_per_step"] * 1e-3) / 1e6) < 0.01 * rec["value"]
+    for k in ("roofline", "parity_mode", "dp_train", "cpu_baseline", "parity"):
+        assert rec[k] is None
+
+    rt.load_tune_cache(os.path.join(ROOT, "profiles", "tune_fwd_bf16_b8_256.json"))
+    net = rgb_net().to(device).set_compute_dtype(torch.bfloat16)
+    x, a = synth_inputs(8, 256, 256, seed=0)
+    xd, ad = x.to(device), a.to(device)
+    _, me = mask_pyramid(ad, 4)
+    with torch.no_grad():
+        want = net(xd, ad, ad, *me)
+    assert sorted(os.listdir(out_dir)) == sorted(f"{n}.npy" for n in OUT_NAMES)
+    for name, w in zip(OUT_NAMES, want):
+        got = np.load(out_dir / f"{name}.npy")
+        assert got.dtype == np.float32 and got.shape == tuple(w.shape)
+        assert np.isfinite(got).all()
+        assert np.array_equal(got, w.float().cpu().numpy()), name

@@ -287,6 +287,33 @@ def test_bench_gpus_flag_spawns_ranks(monkeypatch):
         bench.main()
 
 
+def test_bench_dump_outputs_files_and_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs: one float32 (float64 kept) .npy per name, ranks > 0 under their own
+    file names; an output over its share of the byte budget is cut to the same seeded sample of
+    its elements on every call, so that all files together stay under the budget."""
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(3)
+    big = torch.rand((2, 3, 40, 50), generator=g).to(torch.bfloat16)
+    named = [("x_hat", big), ("bpp", torch.tensor(1.5, dtype=torch.float64)), ("mse", 0.25)]
+    bench.dump_outputs(str(tmp_path / "a"), named)
+    x = np.load(tmp_path / "a" / "x_hat.npy")
+    assert x.dtype == np.float32 and np.array_equal(x, big.float().numpy())
+    assert np.load(tmp_path / "a" / "bpp.npy").dtype == np.float64
+    assert np.load(tmp_path / "a" / "mse.npy") == np.float32(0.25)
+    bench.dump_outputs(str(tmp_path / "a"), named[:1], rank=2)
+    assert (tmp_path / "a" / "x_hat.rank2.npy").exists()
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 3 * 4000)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), named)
+    s1, s2 = np.load(tmp_path / "b" / "x_hat.npy"), np.load(tmp_path / "c" / "x_hat.npy")
+    assert s1.shape == ((3 * 4000 - 4 - 8) // 4,) and np.array_equal(s1, s2)   # what mse, bpp left
+    assert np.isin(s1, x).all() and len(np.unique(s1)) > 100
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= 3 * 4000 + 3 * 128          # the .npy headers
+
+
 def test_masked_ms_ssim_argument_checks():
     """rgbac.metrics.masked_ms_ssim_torch: the reference's shape / window errors
     (masked_ms_ssim_torch.py:148-165, :207-228) and the mask's shape are checked before any

@@ -2,18 +2,20 @@
 # WRITE_SIZE passes over bench.py --train (its eager attribution step between GPU spins),
 # summarised by tools/pmc_traffic.py; "wgrad_kernel" aggregates every weight-gradient kernel
 # (ring, register-staged, patch and halo forms; not the split reductions), matching bench.py's launch label.  GPU only.
+ROOT=$(cd "$(dirname "$0")/.." && pwd); export OUT=${OUT:-$ROOT/bench_out}; mkdir -p "$OUT"
 export TMPDIR=/tmp
 set -e
 for C in FETCH_SIZE WRITE_SIZE; do
-  timeout -s KILL 300 rocprofv3 --pmc $C --output-format csv -d gpurun_out/pmct_$C -o p -- \
-      python bench.py --train --no-cpu-baseline --steps 2 --warmup 1 > gpurun_out/pmct_$C.log 2>&1
+  timeout -s KILL 300 rocprofv3 --pmc $C --output-format csv -d $OUT/pmct_$C -o p -- \
+      python bench.py --full --train --no-cpu-baseline --steps 2 --warmup 1 > $OUT/pmct_$C.log 2>&1
 done
-python tools/pmc_traffic.py gpurun_out/pmct_FETCH_SIZE/p_counter_collection.csv \
-    gpurun_out/pmct_WRITE_SIZE/p_counter_collection.csv gpurun_out/pmc_traffic_train.json 16 256 \
-    > gpurun_out/pmc_traffic_train.txt
+python tools/pmc_traffic.py $OUT/pmct_FETCH_SIZE/p_counter_collection.csv \
+    $OUT/pmct_WRITE_SIZE/p_counter_collection.csv $OUT/pmc_traffic_train.json 16 256 \
+    > $OUT/pmc_traffic_train.txt
 python - <<'PY'
 import json
-p = "gpurun_out/pmc_traffic_train.json"
+import os
+p = os.environ["OUT"] + "/pmc_traffic_train.json"
 d = json.load(open(p))
 k = d["kernels"]
 sel = [v for n, v in k.items() if n.startswith("wgrad_") and "reduce" not in n]
@@ -29,4 +31,4 @@ d["source"] += "; eager training step of bench.py --train (B16, 256x256)"
 json.dump(d, open(p, "w"), indent=1)
 print("wgrad_kernel", k["wgrad_kernel"])
 PY
-rm -rf gpurun_out/pmct_FETCH_SIZE gpurun_out/pmct_WRITE_SIZE
+rm -rf $OUT/pmct_FETCH_SIZE $OUT/pmct_WRITE_SIZE
