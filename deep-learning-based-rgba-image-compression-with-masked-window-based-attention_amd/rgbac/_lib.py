@@ -178,6 +178,12 @@ SIGNATURES = {
     "rgbac_masked_ssim_level": [_I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _F, _F,
                                 _VP, _VP, _VP, _VP],
     "rgbac_masked_msssim_combine": [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP],
+    "rgbac_ssim_level_bwd": [_I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _F, _F, _VP, _VP, _VP,
+                             _VP, _VP, _VP, _VP],
+    "rgbac_masked_ssim_level_bwd": [_I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _F, _F,
+                                    _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP],
+    "rgbac_msssim_combine_bwd": [_I32, _I32, _VP, _VP, _VP, _VP, _I32, _VP, _VP],
+    "rgbac_masked_msssim_combine_bwd": [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _I32, _VP, _VP],
     "rgbac_pmf_to_quantized_cdf": [_VP, _I32, _I32, _VP],
     "rgbac_rans_encoder_create": [ctypes.POINTER(ctypes.c_void_p)],
     "rgbac_rans_encoder_destroy": [_VP],

@@ -668,6 +668,40 @@ int rgbac_masked_msssim_combine(int levels, int batch, int channels, const float
                                 const float* ssim_last, const float* weights, float* per_image,
                                 float* mean, void* stream);
 
+/* Backward of the two metrics above (csrc/msssim_bwd.hip): fp32, no atomics, fixed summation
+ * order.  One level-backward launch per level, coarse to fine; the adjoint of rgbac_avgpool2
+ * is fused in through gc_x / gc_y, the gradient of the next-coarser level's planes
+ * ((h + 2*(h%2) - 2)/2 + 1 by the same in w; NULL at the coarsest level).
+ * rgbac_ssim_level_bwd: dy (and dx when non-NULL; either may be NULL, not both) of one
+ *   rgbac_ssim_level: u_cs[b], u_ssim[b] = gradient of cs_out[b] / ssim_out[b] (NULL = 0).
+ * rgbac_masked_ssim_level_bwd: the same for rgbac_masked_ssim_level; u_cs / u_ssim are per
+ *   (image, channel) plane, partials is the forward's scratch as it left it (the kept-pixel
+ *   counts are read from it), mask the binary level mask; apply_mask != 0 multiplies the
+ *   result by the mask (the adjoint of rgbac_masked_apply, which every ms_ssim level starts with).
+ * rgbac_msssim_combine_bwd: u[l*batch + b] = grad * d value[b] / d mcs[l][b] for l < levels-1
+ *   and u[(levels-1)*batch + b] = grad * d value[b] / d ssim_last[b], of rgbac_msssim_combine's
+ *   product (its broadcast of the ssim factor included); grad: one float (gradient of the batch
+ *   mean, grad_is_mean != 0) or batch floats (gradient of per_image).
+ * rgbac_masked_msssim_combine_bwd: the same per (image, channel) plane, u[l*batch*channels + k],
+ *   with the relu gates: a plane with a factor clamped to 0 gets gradient 0 (torch autograd
+ *   gives 0 * inf = NaN there).  mcs may be NULL when levels == 1. */
+int rgbac_ssim_level_bwd(int batch, int channels, int h, int w, int win_size, const float* x,
+                         const float* y, const float* win, float c1, float c2,
+                         const float* u_cs, const float* u_ssim, const float* gc_x,
+                         const float* gc_y, float* dx, float* dy, void* stream);
+int rgbac_masked_ssim_level_bwd(int batch, int channels, int mask_channels, int h, int w,
+                                int win_size, const float* x, const float* y, const float* mask,
+                                const float* win, float c1, float c2, const float* partials,
+                                const float* u_cs, const float* u_ssim, int apply_mask,
+                                const float* gc_x, const float* gc_y, float* dx, float* dy,
+                                void* stream);
+int rgbac_msssim_combine_bwd(int levels, int batch, const float* mcs, const float* ssim_last,
+                             const float* weights, const float* grad, int grad_is_mean, float* u,
+                             void* stream);
+int rgbac_masked_msssim_combine_bwd(int levels, int batch, int channels, const float* mcs,
+                                    const float* ssim_last, const float* weights,
+                                    const float* grad, int grad_is_mean, float* u, void* stream);
+
 /* Data-parallel gradient exchange (csrc/comm.cpp; BASELINE config 5 -- the reference trains
  * on one GPU, DataParallel is commented out at trainRGB.py:374, so no reference interface is
  * replaced: this is the all-reduce of rgbac/parallel.py's gradient buckets).  RCCL is called
