@@ -13,8 +13,11 @@
 //     4-bit "bypass" digits: the digit count (in runs of 15) then raw_val's nibbles;
 //   * the encoder buffers (start, freq, bypass) records and emits them in reverse at flush;
 //     the stream is the 32-bit words from the final write pointer to the end, little endian.
-// rANS is a single sequential state machine per stream, so this is CPU code: the GPU side
-// of the path (symbols, CDF indexes, dequantisation) is csrc/entropy.hip's rgbac_*_code.
+// One compressai-format stream is a single sequential rANS state machine, so this coder is
+// CPU code; the GPU side of this format's path (symbols, CDF indexes, dequantisation) is
+// csrc/entropy.hip's rgbac_*_code.  The opt-in chunked format (csrc/rans_chunk.h,
+// csrc/rans_dev.hip) cuts the symbols into independent streams of this same algorithm and
+// codes them on the GPU, one lane per chunk; this file is its byte-level oracle per chunk.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -201,6 +201,19 @@ SIGNATURES = {
     "rgbac_rans_decoder_init": [ctypes.POINTER(RansDecoderState), _VP, _I64],
     "rgbac_rans_decode": [ctypes.POINTER(RansDecoderState), _VP, _I64, _VP, _I32, _VP, _VP, _I32,
                           _VP],
+    # chunked rANS coder (csrc/rans_dev.hip): device kernels + their host twins
+    "rgbac_rans_chunk_sizes": [_VP, _VP, _I64, _I64, _VP, _VP, _I64, _I32, _VP, _I32, _VP, _VP,
+                               _I32, _VP, _VP, _VP],
+    "rgbac_rans_chunk_encode": [_VP, _VP, _I64, _I64, _VP, _VP, _I64, _I32, _VP, _I32, _VP, _VP,
+                                _I32, _VP, _VP, _VP, _I64, _VP, _VP],
+    "rgbac_rans_chunk_decode": [_VP, _I64, _VP, _VP, _VP, _I64, _I64, _VP, _VP, _I64, _I32, _VP,
+                                _I32, _VP, _VP, _I32, _VP, _VP, _VP],
+    "rgbac_rans_chunk_encode_host": [_VP, _VP, _I64, _I64, _VP, _VP, _I64, _I32, _VP, _I32, _VP,
+                                     _VP, _I32, _VP, _VP, _I64, ctypes.POINTER(ctypes.c_int64),
+                                     ctypes.POINTER(ctypes.c_int32)],
+    "rgbac_rans_chunk_decode_host": [_VP, _I64, _VP, _VP, _VP, _I64, _I64, _VP, _VP, _I64, _I32,
+                                     _VP, _I32, _VP, _VP, _I32, _VP,
+                                     ctypes.POINTER(ctypes.c_int32)],
 }
 _RESTYPE = {"rgbac_last_error": ctypes.c_char_p, "rgbac_rans_encoder_bound": ctypes.c_int64,
             "rgbac_winattn_block_workspace": ctypes.c_int64}

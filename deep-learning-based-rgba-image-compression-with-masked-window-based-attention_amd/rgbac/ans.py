@@ -7,6 +7,11 @@ entropy models use ``RansEncoder.encode_with_indexes`` / ``RansDecoder.decode_wi
 and ``_CXX.pmf_to_quantized_cdf``.  Same class / method names and argument meaning; the
 coder itself is csrc/rans.cpp (C ABI in include/rgbac.h), byte-compatible with compressai's.
 Arguments may be Python lists (as the reference passes them) or numpy / torch int tensors.
+
+Below that surface: the opt-in chunked stream format and its device-side coder
+(``encode_chunked``, ``ChunkedDecoder``, ``DeviceCdfTables`` over csrc/rans_dev.hip; the CPU
+twins ``encode_chunked_host`` / ``decode_chunked_host``), used by compress / decompress with
+coder="device".
 """
 import ctypes
 
@@ -134,3 +139,291 @@ class RansDecoder:
     def decode_with_indexes(self, encoded, indexes, cdfs, cdf_lengths=None, offsets=None):
         self.set_stream(encoded)
         return self.decode_stream(indexes, cdfs, cdf_lengths, offsets)
+
+
+# ---------------------------------------------------------------------------------------------
+# Chunked stream format: the device-side coder (csrc/rans_dev.hip) and its host twin.
+#
+# The symbol sequence of a container is ``nseg`` segments; every segment is cut into chunks of
+# K symbols (its last chunk may be short) and every chunk is an independent rANS stream, coded
+# by one GPU lane.  Container, little-endian u32 words:
+#     magic, version (1), K, nseg, nseg symbol counts,
+#     then for every chunk in segment order its word count, then the chunks' words.
+# The bytes of a chunk are exactly ``RansEncoder().encode_with_indexes(sym[chunk], idx[chunk],
+# tables)``, so the size is fixed by the format: header + 4 bytes per chunk of count table +
+# each chunk's own 8-byte final state and tail word, i.e. at most 12 bytes per chunk over one
+# long stream.  K trades rate against parallelism: a smaller K costs up to 12 bytes more per K
+# symbols and gives n / K lanes; the 655,360 y symbols of eight 256 x 256 images are 640 lanes
+# at K = 1024 (<= 0.1 bit per symbol of overhead) and 2,560 lanes at K = 256 (<= 0.4 bit).
+CHUNK_MAGIC = 0x43524752            # b"RGRC"
+CHUNK_VERSION = 1
+CHUNK_ERRORS = {1: "read past the end of a chunk", 2: "CDF index out of range",
+                3: "corrupt stream or CDF table", 4: "corrupt bypass length",
+                5: "chunk table or offsets out of range"}
+
+
+def _chunk_table(seg_lengths, chunk):
+    """-> (seg_lengths int64, per-segment first chunk (nseg + 1), table int64 (2, nchunks):
+    row 0 each chunk's first symbol in the container's sequence, row 1 its length)."""
+    seg = np.asarray(list(seg_lengths), dtype=np.int64).reshape(-1)
+    chunk = int(chunk)
+    if chunk <= 0 or chunk >= 1 << 31:
+        raise ValueError("chunk size must be a positive 32-bit number")
+    if seg.size == 0 or (seg <= 0).any():
+        raise ValueError("a container needs at least one segment, each of at least one symbol")
+    per = (seg + chunk - 1) // chunk
+    first = np.concatenate([[0], np.cumsum(per)]).astype(np.int64)
+    base = np.concatenate([[0], np.cumsum(seg)[:-1]]).astype(np.int64)
+    which = np.repeat(np.arange(seg.size), per)
+    k = np.arange(int(first[-1]), dtype=np.int64) - first[which]
+    tab = np.empty((2, int(first[-1])), dtype=np.int64)
+    tab[0] = base[which] + k * chunk
+    tab[1] = np.minimum(chunk, seg[which] - k * chunk)
+    return seg, first, tab
+
+
+def _header(chunk, seg):
+    return np.concatenate([[CHUNK_MAGIC, CHUNK_VERSION, int(chunk), seg.size], seg]).astype("<u4")
+
+
+def _raise_code(what, code):
+    if code:
+        raise RuntimeError(f"{what}: error {code} ({CHUNK_ERRORS.get(code, 'unknown')})")
+
+
+class ChunkedLayout:
+    """A parsed and validated container: K, seg_lengths, counts (words per chunk), offsets
+    (first word of each chunk in the payload), payload (uint32), first (per-segment first
+    chunk) and table (see _chunk_table).  Anything wrong raises RuntimeError."""
+
+    def __init__(self, blob):
+        blob = bytes(blob)
+        if len(blob) % 4 != 0 or len(blob) < 20:
+            raise RuntimeError("chunked stream: length must be whole 32-bit words, >= 20 bytes")
+        w = np.frombuffer(blob, dtype="<u4")
+        if int(w[0]) != CHUNK_MAGIC:
+            raise RuntimeError("chunked stream: bad magic (not a chunked container)")
+        if int(w[1]) != CHUNK_VERSION:
+            raise RuntimeError(f"chunked stream: unsupported version {int(w[1])}")
+        K, nseg = int(w[2]), int(w[3])
+        if K <= 0 or K >= 1 << 31 or nseg <= 0 or 4 + nseg > w.size:
+            raise RuntimeError("chunked stream: bad chunk size or segment count")
+        seg = w[4:4 + nseg].astype(np.int64)
+        if (seg <= 0).any():
+            raise RuntimeError("chunked stream: empty segment")
+        self.K = K
+        self.seg_lengths, self.first, self.table = _chunk_table(seg, K)
+        nchunks = int(self.first[-1])
+        body = 4 + nseg
+        if body + nchunks > w.size:
+            raise RuntimeError("chunked stream: the chunk count disagrees with the segment "
+                               "lengths (count table longer than the stream)")
+        self.counts = w[body:body + nchunks].astype(np.int64)
+        self.payload = np.ascontiguousarray(w[body + nchunks:]).astype(np.uint32)
+        # every chunk holds its two state words and at most 10 words per symbol
+        if (self.counts < 2).any() or (self.counts > 10 * self.table[1] + 2).any():
+            raise RuntimeError("chunked stream: the chunk count disagrees with the segment "
+                               "lengths (a chunk's word count is impossible for its length)")
+        total = int(self.counts.sum())
+        if total != self.payload.size:
+            raise RuntimeError(f"chunked stream: the counts sum to {total} words, the payload "
+                               f"has {self.payload.size}")
+        if total == 0:
+            raise RuntimeError("chunked stream: empty payload")
+        self.offsets = (np.cumsum(self.counts) - self.counts).astype(np.int64)
+        self.seg_base = np.concatenate([[0], np.cumsum(self.seg_lengths)]).astype(np.int64)
+
+    def chunk_bytes(self, c):
+        o, n = int(self.offsets[c]), int(self.counts[c])
+        return self.payload[o:o + n].astype("<u4").tobytes()
+
+
+class DeviceCdfTables:
+    """The (cdfs, lengths, offsets) triple resident on a device, for the chunked kernels;
+    built from (and validated like) a CdfTables."""
+
+    def __init__(self, tables, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("DeviceCdfTables needs a GPU device (there is no CPU path)")
+        tab = CdfTables.of(tables)
+        stride = int(tab.cdfs.shape[1])
+        if stride < 3 or (tab.sizes < 3).any() or (tab.sizes > stride).any():
+            raise ValueError("CDF length out of range")
+        self.device = device
+        self.stride, self.ncdf = stride, int(tab.cdfs.shape[0])
+        self.cdfs = torch.from_numpy(tab.cdfs).to(device)
+        self.sizes = torch.from_numpy(tab.sizes).to(device)
+        self.offsets = torch.from_numpy(tab.offsets).to(device)
+
+    def args(self):
+        return (self.cdfs.data_ptr(), self.stride, self.sizes.data_ptr(),
+                self.offsets.data_ptr(), self.ncdf)
+
+
+def _dev_i32(t, what):
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise RuntimeError(f"{what} must be a GPU tensor (the device coder has no CPU path; "
+                           "use encode_chunked_host / decode_chunked_host)")
+    if t.dtype != torch.int32:
+        raise TypeError(f"{what} must be int32")
+    return t.contiguous().view(-1)
+
+
+def _upload(arr, device):
+    """Host array -> device without stalling the host on queued GPU work."""
+    return torch.from_numpy(arr).pin_memory().to(device, non_blocking=True)
+
+
+def encode_chunked_many(jobs, chunk):
+    """jobs: [(symbols, indexes, DeviceCdfTables, seg_lengths), ...] -> [bytes, ...], one
+    container per job.  All jobs share the host reads: the containers' sizes (a few bytes),
+    then one device->host copy of all finished containers."""
+    if not jobs:
+        return []
+    prep = []
+    dev = None
+    for sym, idx, tab, seg_lengths in jobs:
+        sym, idx = _dev_i32(sym, "symbols"), _dev_i32(idx, "indexes")
+        if not isinstance(tab, DeviceCdfTables):
+            raise TypeError("encode_chunked needs DeviceCdfTables")
+        if dev is None:
+            dev = sym.device
+        if idx.device != dev or sym.device != dev or tab.device != dev:
+            raise RuntimeError("symbols, indexes and tables must live on one device")
+        seg, _, table = _chunk_table(seg_lengths, chunk)
+        if sym.numel() != idx.numel() or sym.numel() != int(seg.sum()):
+            raise ValueError("symbols, indexes and seg_lengths disagree on the symbol count")
+        prep.append((sym, idx, tab, seg, table))
+    stream = _lib.stream_ptr(dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    queued = []
+    for sym, idx, tab, seg, table in prep:
+        nch = table.shape[1]
+        tdev = _upload(table, dev)
+        counts = torch.empty(nch, dtype=torch.int32, device=dev)
+        head = (sym.data_ptr(), idx.data_ptr(), int(sym.numel()), 0, tdev[0].data_ptr(),
+                tdev[1].data_ptr(), nch, int(chunk)) + tab.args()
+        _lib.call("rgbac_rans_chunk_sizes", *head, counts.data_ptr(), err.data_ptr(), stream)
+        ends = torch.cumsum(counts, 0, dtype=torch.int64)
+        queued.append((head, counts, ends, tdev))
+    totals = torch.stack([q[2][-1] for q in queued]).cpu().tolist()   # the sizes: one read
+    # one buffer: per job its count table then its words; the error word last
+    spans, pos = [], 0
+    for (head, counts, ends, _), total in zip(queued, totals):
+        spans.append((pos, counts.numel(), int(total)))
+        pos += counts.numel() + int(total)
+    out = torch.empty(pos + 1, dtype=torch.int32, device=dev)
+    for (head, counts, ends, _), (p, nch, total) in zip(queued, spans):
+        out[p:p + nch].copy_(counts)
+        _lib.call("rgbac_rans_chunk_encode", *head, counts.data_ptr(), ends.data_ptr(),
+                  out[p + nch:].data_ptr(), total, err.data_ptr(), stream)
+    out[pos:].copy_(err)
+    host = out.cpu().numpy()                                          # the bytes: one copy
+    _raise_code("encode_chunked", int(host[pos]))
+    blobs = []
+    for (_, _, _, seg, _), (p, nch, total) in zip(prep, spans):
+        blobs.append(_header(chunk, seg).tobytes() + host[p:p + nch + total].astype("<i4").tobytes())
+    return blobs
+
+
+def encode_chunked(symbols, indexes, tables, seg_lengths, chunk=256):
+    """Device int32 symbols / indexes (sum(seg_lengths) each, segments back to back) -> the
+    container's bytes.  Two kernel passes (sizes, then encode into the scanned offsets); the
+    host reads the total size, then copies the finished bytes once."""
+    return encode_chunked_many([(symbols, indexes, tables, seg_lengths)], chunk)[0]
+
+
+class ChunkedDecoder:
+    """Decodes one container on the device.  The header is parsed and validated on the host
+    (RuntimeError before any launch); payload, offsets, counts and the chunk table are uploaded
+    once.  ``decode_segments`` only queues a kernel; ``check()`` reads the error word.  Several
+    decoders may share one error word (``err``)."""
+
+    def __init__(self, blob, device, err=None):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("ChunkedDecoder needs a GPU device (there is no CPU path; "
+                               "use decode_chunked_host)")
+        lay = ChunkedLayout(blob)
+        self.layout, self.device = lay, device
+        self.K, self.seg_lengths = lay.K, lay.seg_lengths.tolist()
+        self._payload = torch.from_numpy(lay.payload.view(np.int32)).to(device)
+        meta = np.stack([lay.offsets, lay.table[0], lay.table[1]])
+        self._meta = torch.from_numpy(meta).to(device)               # int64 (3, nchunks)
+        self._counts = torch.from_numpy(lay.counts.astype(np.int32)).to(device)
+        self._err = err if err is not None else torch.zeros(1, dtype=torch.int32, device=device)
+
+    def decode_segments(self, lo, hi, indexes, tables, out=None):
+        """Symbols of segments lo..hi-1 (device int32, flat) from their CDF indexes; no sync."""
+        lay = self.layout
+        if not 0 <= lo < hi <= len(self.seg_lengths):
+            raise ValueError("segment range")
+        idx = _dev_i32(indexes, "indexes")
+        if not isinstance(tables, DeviceCdfTables):
+            raise TypeError("decode_segments needs DeviceCdfTables")
+        base, nsym = int(lay.seg_base[lo]), int(lay.seg_base[hi] - lay.seg_base[lo])
+        if idx.numel() != nsym:
+            raise RuntimeError(f"chunked stream: segments {lo}..{hi - 1} hold {nsym} symbols, "
+                               f"{idx.numel()} indexes given")
+        if out is None:
+            out = torch.empty(nsym, dtype=torch.int32, device=self.device)
+        elif (out.dtype != torch.int32 or out.device != idx.device or out.numel() != nsym
+              or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous device int32 tensor of the segments' size")
+        c0, c1 = int(lay.first[lo]), int(lay.first[hi])
+        m = self._meta
+        _lib.call("rgbac_rans_chunk_decode", self._payload.data_ptr(), int(self._payload.numel()),
+                  m[0, c0:].data_ptr(), self._counts[c0:].data_ptr(), idx.data_ptr(), nsym, base,
+                  m[1, c0:].data_ptr(), m[2, c0:].data_ptr(), c1 - c0, self.K, *tables.args(),
+                  out.data_ptr(), self._err.data_ptr(), _lib.stream_ptr(self.device))
+        return out
+
+    def check(self):
+        """Reads the error word (a sync); raises RuntimeError naming the first error code."""
+        _raise_code("chunked stream decode", int(self._err.item()))
+
+
+def encode_chunked_host(symbols, indexes, tables, seg_lengths, chunk=256,
+                        cdf_lengths=None, offsets=None):
+    """encode_chunked on the CPU (the same coder core in a loop over chunks): for tests and
+    for writing streams without a GPU.  The device path never calls it."""
+    s, i = _i32(symbols), _i32(indexes)
+    tab = CdfTables.of(tables, cdf_lengths, offsets)
+    seg, _, table = _chunk_table(seg_lengths, chunk)
+    if s.size != i.size or s.size != int(seg.sum()):
+        raise ValueError("symbols, indexes and seg_lengths disagree on the symbol count")
+    nch = table.shape[1]
+    counts = np.zeros(nch, dtype=np.int32)
+    total, err = ctypes.c_int64(0), ctypes.c_int32(0)
+    head = (s.ctypes.data, i.ctypes.data, int(s.size), 0, table[0].ctypes.data,
+            table[1].ctypes.data, nch, int(chunk)) + tab.args()
+    _lib.call("rgbac_rans_chunk_encode_host", *head, counts.ctypes.data, None, 0,
+              ctypes.byref(total), ctypes.byref(err))
+    _raise_code("encode_chunked_host", err.value)
+    payload = np.zeros(total.value, dtype=np.uint32)
+    _lib.call("rgbac_rans_chunk_encode_host", *head, counts.ctypes.data, payload.ctypes.data,
+              int(payload.size), ctypes.byref(total), ctypes.byref(err))
+    _raise_code("encode_chunked_host", err.value)
+    return (_header(chunk, seg).tobytes() + counts.astype("<i4").tobytes()
+            + payload.astype("<u4").tobytes())
+
+
+def decode_chunked_host(blob, indexes, tables, cdf_lengths=None, offsets=None):
+    """Decodes a whole container on the CPU -> int32 array of all segments' symbols."""
+    lay = ChunkedLayout(blob)
+    i = _i32(indexes)
+    tab = CdfTables.of(tables, cdf_lengths, offsets)
+    nsym = int(lay.seg_base[-1])
+    if i.size != nsym:
+        raise RuntimeError(f"chunked stream: the container holds {nsym} symbols, "
+                           f"{i.size} indexes given")
+    out = np.empty(nsym, dtype=np.int32)
+    counts = lay.counts.astype(np.int32)
+    err = ctypes.c_int32(0)
+    _lib.call("rgbac_rans_chunk_decode_host", lay.payload.ctypes.data, int(lay.payload.size),
+              lay.offsets.ctypes.data, counts.ctypes.data, i.ctypes.data, nsym, 0,
+              lay.table[0].ctypes.data, lay.table[1].ctypes.data, int(lay.first[-1]), lay.K,
+              *tab.args(), out.ctypes.data, ctypes.byref(err))
+    _raise_code("chunked stream decode", err.value)
+    return out

@@ -84,6 +84,18 @@ class _EntropyModel(nn.Module):
             self.__dict__["_rgbac_tables"] = ent
         return ent[2]
 
+    def device_tables(self, device):
+        """The same tables resident on ``device`` for the chunked device coder (cached like
+        tables(): buffer identity plus _version, so update() invalidates it)."""
+        from .ans import DeviceCdfTables
+        host = self.tables()
+        device = torch.device(device)
+        ent = self.__dict__.get("_rgbac_dev_tables")
+        if ent is None or ent[0] is not host or ent[1] != device:
+            ent = (host, device, DeviceCdfTables(host, device))
+            self.__dict__["_rgbac_dev_tables"] = ent
+        return ent[2]
+
     def quantize(self, inputs, mode, means=None):
         """EntropyModel.quantize for mode "symbols" / "dequantize" (inference)."""
         if mode not in ("symbols", "dequantize"):

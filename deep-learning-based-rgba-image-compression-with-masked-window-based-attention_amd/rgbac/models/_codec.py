@@ -16,12 +16,20 @@ Same dataflow as the reference, restructured like the forward's latent path (_la
     (a CDF index computed from a scale that differs in the last bit desynchronises rANS).
 The strings are compressai's: strings[0] = [one y string for the batch, slices in order,
 NCHW within a slice] (:354-355,:367-369), strings[1] = one z string per image (:319).
+
+coder="device" (opt-in) keeps the same symbols but writes the chunked stream format of
+rgbac.ans / csrc/rans_dev.hip instead: strings[0] = [one container with num_slices segments,
+a slice's B*cs*h*w symbols each], strings[1] = one single-segment container per image.  The
+coder then runs on the GPU, one lane per chunk: compress reads back the containers' sizes and
+then the finished bytes, decompress uploads the bytes and does not return to the host until
+x_hat is queued (one read of the error word at the end).  The default coder="host" is the
+compressai format above, unchanged.
 """
 import torch
 
 from .. import _lib
 from .. import runtime as rt
-from ..ans import BufferedRansEncoder, RansDecoder
+from ..ans import BufferedRansEncoder, ChunkedDecoder, RansDecoder, encode_chunked_many
 from ..layers.SupplyMask import mask_pyramid
 from ..layers.TransformRGB import prep_conv
 from ._latent import _hyper_a, _hyper_s_pair, _musigma_pack
@@ -47,10 +55,11 @@ def _gauss_code(gc, mode, y, ycoff, ms, cs, sym, idx, pre):
     return st
 
 
-def latent_code(model, y=None, z_sym=None, z_shape=None, y_decoder=None):
+def latent_code(model, y=None, z_sym=None, z_shape=None, y_decoder=None, y_chunked=None):
     """compress (y given): -> (YH, z_sym, y_sym, y_idx); decompress (z_sym + y_decoder
     given): -> (YH, z_sym, y_sym, y_idx) with y_sym decoded.  z_sym int32 (B, C, h, w) NCHW,
-    y_sym / y_idx int32 (num_slices, B*cs*H*W) in the reference's stream order."""
+    y_sym / y_idx int32 (num_slices, B*cs*H*W) in the reference's stream order.
+    ``y_chunked`` (a ChunkedDecoder, in place of y_decoder) decodes each wave on the device."""
     eb, gc = model.entropy_bottleneck, model.gaussian_conditional
     encode = y is not None
     ns, msup, M = model.num_slices, model.max_support_slices, model.M
@@ -79,7 +88,10 @@ def latent_code(model, y=None, z_sym=None, z_shape=None, y_decoder=None):
         waves = [[i] for i in range(min(msup, ns))]
         if ns > msup:
             waves.append(list(range(msup, ns)))
-        tables = None if encode else gc.tables()
+        if encode:
+            tables = None
+        else:
+            tables = gc.tables() if y_chunked is None else gc.device_tables(dev)
         for wave in waves:
             sup = [cs * min(i, msup) for i in wave]
             k = len(wave)
@@ -107,9 +119,12 @@ def latent_code(model, y=None, z_sym=None, z_shape=None, y_decoder=None):
                 for j, i in enumerate(wave):
                     _gauss_code(gc, 1, None, 0, mss[j], cs, None, y_idx[i], None)
                 lo, hi = wave[0], wave[-1] + 1
-                idx_host = y_idx[lo:hi].cpu()                   # one sync per wave
-                sym = y_decoder.decode_stream_np(idx_host.reshape(-1).numpy(), tables)
-                y_sym[lo:hi].copy_(torch.from_numpy(sym).view(hi - lo, n))
+                if y_chunked is not None:                       # device coder: no sync
+                    y_chunked.decode_segments(lo, hi, y_idx[lo:hi], tables, out=y_sym[lo:hi])
+                else:
+                    idx_host = y_idx[lo:hi].cpu()               # one sync per wave
+                    sym = y_decoder.decode_stream_np(idx_host.reshape(-1).numpy(), tables)
+                    y_sym[lo:hi].copy_(torch.from_numpy(sym).view(hi - lo, n))
                 for j, i in enumerate(wave):
                     _gauss_code(gc, 2, None, 0, mss[j], cs, y_sym[i], None, pres[j])
             # lrp stacks: y_hat_i = (y_q + mu) + 0.5 * tanh(lrp([means, y_hat_<i, y_q + mu]))
@@ -130,8 +145,21 @@ def _check(model, *ts):
     model.entropy_bottleneck._check_cdf()
 
 
-def compress(model, input, mask):
-    """:312-371 -> {"strings": [[y_string], z_strings], "shape": z spatial size}."""
+def _coder(coder):
+    if coder not in ("host", "device"):
+        raise ValueError(f"coder must be 'host' or 'device', got {coder!r}")
+    return coder == "device"
+
+
+def _z_indexes(C, hw, device=None):
+    return torch.arange(C, dtype=torch.int32, device=device).view(C, 1).expand(C, hw).reshape(-1)
+
+
+def compress(model, input, mask, coder="host", chunk=256):
+    """:312-371 -> {"strings": [[y_string], z_strings], "shape": z spatial size}; with
+    coder="device" the strings are chunked containers (chunks of ``chunk`` symbols) and the
+    dict also holds "coder": "device"."""
+    device_coder = _coder(coder)
     _check(model, input, mask)
     B, _, H, W = input.shape
     from .AutoEncoderRGB_Journal import check_geometry
@@ -141,6 +169,8 @@ def compress(model, input, mask):
         _, me = mask_pyramid(mask, 4)                            # EncMakeMask(mask) (:314)
         y = model.Encoder.nhwc(xf, me[1], me[2])                 # :315
         _, z_sym, y_sym, y_idx = latent_code(model, y=y)
+        if device_coder:
+            return _compress_device(model, z_sym, y_sym, y_idx, chunk)
         z_host, ys_host, yi_host = z_sym.cpu(), y_sym.cpu(), y_idx.cpu()   # one sync
     eb = model.entropy_bottleneck
     C, zh, zw = z_host.shape[1:]
@@ -157,9 +187,57 @@ def compress(model, input, mask):
     return {"strings": [[enc.flush()], z_strings], "shape": torch.Size((zh, zw))}
 
 
-def decompress(model, strings, shape, mask):
-    """:373-416 -> {"x_hat": (B,3,H,W) clamped to [0, 1]}; B = len(strings[1])."""
+def _compress_device(model, z_sym, y_sym, y_idx, chunk):
+    """The chunked containers of one batch: the y container (one segment per slice) and one z
+    container per image, all coded on the device and brought back with one copy."""
+    eb, gc = model.entropy_bottleneck, model.gaussian_conditional
+    dev = z_sym.device
+    B, C, zh, zw = z_sym.shape
+    z_idx = _z_indexes(C, zh * zw, dev)
+    z_tab, y_tab = eb.device_tables(dev), gc.device_tables(dev)
+    ns, n = y_sym.shape
+    jobs = [(y_sym, y_idx, y_tab, [n] * ns)]
+    jobs += [(z_sym[b], z_idx, z_tab, [C * zh * zw]) for b in range(B)]
+    blobs = encode_chunked_many(jobs, chunk)
+    return {"strings": [[blobs[0]], blobs[1:]], "shape": torch.Size((zh, zw)),
+            "coder": "device"}
+
+
+def _decompress_device(model, strings, zh, zw, mask):
+    eb, gc = model.entropy_bottleneck, model.gaussian_conditional
+    dev = mask.device
+    B, C = len(strings[1]), eb.channels
+    if len(strings[0]) != 1:
+        raise RuntimeError("decompress: strings[0] must hold one y container")
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    # every header is validated (RuntimeError) and every byte uploaded before the first launch
+    z_decs = [ChunkedDecoder(s, dev, err=err) for s in strings[1]]
+    y_dec = ChunkedDecoder(strings[0][0], dev, err=err)
+    if len(y_dec.seg_lengths) != model.num_slices:
+        raise RuntimeError(f"decompress: the y container has {len(y_dec.seg_lengths)} segments, "
+                           f"the model {model.num_slices} slices")
+    z_idx = _z_indexes(C, zh * zw, dev)
+    z_tab = eb.device_tables(dev)
+    z_sym = torch.empty((B, C, zh, zw), dtype=torch.int32, device=dev)
+    with torch.no_grad():
+        for b, d in enumerate(z_decs):
+            d.decode_segments(0, 1, z_idx, z_tab, out=z_sym[b])
+        YH, _, _, _ = latent_code(model, z_sym=z_sym, y_chunked=y_dec)
+        _, md = mask_pyramid(mask, 4)
+        xh = model.Decoder.nhwc(YH, md[1], md[2])
+        x_hat = rt.to_nchw(xh).clamp_(0, 1)
+    y_dec.check()                    # the shared error word, once the synthesis is queued
+    return {"x_hat": x_hat}
+
+
+def decompress(model, strings, shape, mask, coder="host"):
+    """:373-416 -> {"x_hat": (B,3,H,W) clamped to [0, 1]}; B = len(strings[1]).  coder must
+    name the format compress wrote: a host-format string given to coder="device" (or the
+    reverse) is rejected."""
+    device_coder = _coder(coder)
     _check(model, mask)
+    if device_coder:
+        return _decompress_device(model, strings, int(shape[0]), int(shape[1]), mask)
     eb = model.entropy_bottleneck
     zh, zw = int(shape[0]), int(shape[1])
     B = len(strings[1])

@@ -748,6 +748,58 @@ int rgbac_rans_decode(rgbac_rans_decoder_t* dec, const int32_t* indexes, int64_t
                       const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
                       const int32_t* offsets, int ncdf, int32_t* out);
 
+/* Device-side chunked rANS coder (csrc/rans_dev.hip over csrc/rans_chunk.h): the opt-in second
+ * stream format of compress / decompress (coder="device").  The symbol sequence is cut into
+ * chunks of at most K symbols; every chunk is an independent stream of the coder above (its
+ * words are what rgbac_rans_encoder_flush returns for the chunk's symbols), coded by one GPU
+ * lane.  Chunk c covers symbols [chunk_start[c], chunk_start[c] + chunk_len[c]) of the
+ * container's sequence; symbols / indexes / out address symbol sym_base of it and hold nsym
+ * entries.  All pointers are device pointers (CDF tables included); err is one int32 the caller
+ * zeroes: the first non-zero code (1 read past a chunk's end, 2 CDF index out of range,
+ * 3 corrupt stream or table, 4 corrupt bypass length, 5 chunk table / offsets out of range)
+ * is left there, and an erring chunk decodes to zeros from the error on.
+ *   rgbac_rans_chunk_sizes : counts[c] = words of chunk c (the state machine without stores)
+ *   rgbac_rans_chunk_encode: stores chunk c's words into payload[ends[c] - counts[c], ends[c])
+ *                            (ends = running sum of counts)
+ *   rgbac_rans_chunk_decode: chunk c's words are payload[word_off[c], word_off[c] + counts[c])
+ * The *_host entry points run the same core in a CPU loop on host pointers (tests, reading a
+ * stream without a GPU; the device path never calls them).  rgbac_rans_chunk_encode_host packs
+ * the chunks in order; payload == NULL returns counts and *total_words only. */
+int rgbac_rans_chunk_sizes(const int32_t* symbols, const int32_t* indexes, int64_t nsym,
+                           int64_t sym_base, const int64_t* chunk_start,
+                           const int64_t* chunk_len, int64_t nchunks, int K,
+                           const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                           const int32_t* offsets, int ncdf, int32_t* counts, int32_t* err,
+                           void* stream);
+int rgbac_rans_chunk_encode(const int32_t* symbols, const int32_t* indexes, int64_t nsym,
+                            int64_t sym_base, const int64_t* chunk_start,
+                            const int64_t* chunk_len, int64_t nchunks, int K,
+                            const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                            const int32_t* offsets, int ncdf, const int32_t* counts,
+                            const int64_t* ends, uint32_t* payload, int64_t payload_words,
+                            int32_t* err, void* stream);
+int rgbac_rans_chunk_decode(const uint32_t* payload, int64_t payload_words,
+                            const int64_t* word_off, const int32_t* counts,
+                            const int32_t* indexes, int64_t nsym, int64_t sym_base,
+                            const int64_t* chunk_start, const int64_t* chunk_len,
+                            int64_t nchunks, int K, const int32_t* cdfs, int cdf_stride,
+                            const int32_t* cdf_sizes, const int32_t* offsets, int ncdf,
+                            int32_t* out, int32_t* err, void* stream);
+int rgbac_rans_chunk_encode_host(const int32_t* symbols, const int32_t* indexes, int64_t nsym,
+                                 int64_t sym_base, const int64_t* chunk_start,
+                                 const int64_t* chunk_len, int64_t nchunks, int K,
+                                 const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                                 const int32_t* offsets, int ncdf, int32_t* counts,
+                                 uint32_t* payload, int64_t payload_words, int64_t* total_words,
+                                 int32_t* err);
+int rgbac_rans_chunk_decode_host(const uint32_t* payload, int64_t payload_words,
+                                 const int64_t* word_off, const int32_t* counts,
+                                 const int32_t* indexes, int64_t nsym, int64_t sym_base,
+                                 const int64_t* chunk_start, const int64_t* chunk_len,
+                                 int64_t nchunks, int K, const int32_t* cdfs, int cdf_stride,
+                                 const int32_t* cdf_sizes, const int32_t* offsets, int ncdf,
+                                 int32_t* out, int32_t* err);
+
 #ifdef __cplusplus
 }
 #endif
