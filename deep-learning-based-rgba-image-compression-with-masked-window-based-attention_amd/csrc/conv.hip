@@ -37,7 +37,9 @@
 // group, split, phase).  The model uses it for the cc_mean/cc_scale stacks,
 // the conv_a/conv_b residual units and h_mean_s/h_scale_s, which are
 // independent chains of identical shape.
+#include <cstdio>
 #include <cstdlib>
+#include <utility>
 
 #include "common.h"
 #include "conv_common.h"
@@ -1041,72 +1043,92 @@ __global__ void __launch_bounds__(256, 4) conv3x3_c32_kernel(const ConvArgsDev a
 }
 
 template <typename T, int NT>
-static void launch_direct(const ConvArgsDev& d, dim3 grid, int rs, int nks_max, hipStream_t st) {
+static void launch_direct(const ConvArgsDev& d, dim3 grid, int rs, hipStream_t st) {
   constexpr int NKS = 12;
   const size_t lds = (size_t)16 * NT * rs * 16;
-  (void)nks_max;
   hipLaunchKernelGGL((conv_direct_kernel<T, NT, NKS>), grid, dim3(256), lds, st, d, rs);
 }
 
-struct TileCfg { int bm, bn; };
-// 0..6: streaming K-ring kernel; 7..12: weight-resident persistent kernel (kWresStages)
-static const TileCfg kTiles[] = {
-    {128, 128}, {128, 64}, {64, 64}, {128, 32}, {64, 32}, {128, 16}, {64, 16},
-    {128, 64}, {64, 64}, {128, 32}, {64, 32}, {128, 128}, {128, 16},
-    {16, 16}, {16, 32}, {16, 48}, {16, 64}, {16, 96}, {16, 192},
-    {256, 32},
+// ---------------------------------------------------------------------------
+// The tile table: the ONE place a conv tile is described.  rgbac_conv_args.tile indexes it.
+// plan_conv (end of this file) reads a tile's kind and shape to validate a launch and to pick
+// the kernel instantiation, launch_tile takes the kernels' template arguments from it, and
+// rgbac_conv_tile_info hands (bm, bn, kind) to the host runtime.
+enum TileKind : int {
+  kStream = RGBAC_TILE_STREAM,      // conv_kernel: streaming K ring, 128-byte K stages
+  kDeep = RGBAC_TILE_DEEP,          // conv_kernel with 256-byte K stages (KSM = 2)
+  kPers = RGBAC_TILE_PERS,          // conv_pers_kernel: persistent over output tiles (no GAUSS)
+  kWres = RGBAC_TILE_WRES,          // conv_wres_kernel: weight-resident, K <= kWresStages stages
+  kDirect = RGBAC_TILE_DIRECT,      // conv_direct_kernel: NT = bn / 16, K <= kDirectSteps k-steps
+  kSpatial = RGBAC_TILE_SPATIAL,    // conv3x3_c32_kernel (16x16 pixels x 32 channels)
+  kSmallK = RGBAC_TILE_SMALLK,      // conv_smallk_kernel (bf16 1x1, one source, K <= 256)
+  kWStream = RGBAC_TILE_WSTREAM,    // conv_wstream_kernel (bf16, stride 1, k 1/3, cout <= 32)
+  kPatch = RGBAC_TILE_PATCH,        // conv_patch_kernel (bf16; k3 s1 conv/subpel, convT, 5x5/s2)
+  kFPatch = RGBAC_TILE_FPATCH,      // conv_fpatch_kernel (fragment-major weights, 4 waves)
+  kFPatchKS = RGBAC_TILE_FPATCH_KS, // conv_fpatch_kernel, unrolled K split by kernel row (KS = 3)
+  kPW = RGBAC_TILE_PW,              // conv_pw / pw2 / pw3_kernel (bf16 1x1, cin/cout <= 192)
+  kNPatch = RGBAC_TILE_NPATCH,      // conv_npatch_kernel (bf16 3x3 s1, cout <= 32, fragment-major)
+};
+struct TileDesc {
+  int kind, bm, bn;   // pixels x channels (patch kinds: bm = TH rows of 16 pixels)
+  int a, b, c;        // stream / deep / pers / wres / patch: WGM, WGN, NBUF (wres: none);
+};                    // fpatch-ks: a = N waves (x 3 K parts), b = has the CPT 8..10 variants
+constexpr TileDesc kTiles[] = {
+    {kStream, 128, 128, 2, 2, 2}, {kStream, 128, 64, 4, 1, 3}, {kStream, 64, 64, 2, 2, 3},
+    {kStream, 128, 32, 4, 1, 3}, {kStream, 64, 32, 2, 2, 3}, {kStream, 128, 16, 4, 1, 3},
+    {kStream, 64, 16, 4, 1, 3},
+    {kWres, 128, 64, 2, 2}, {kWres, 64, 64, 2, 2}, {kWres, 128, 32, 4, 1}, {kWres, 64, 32, 2, 2},
+    {kWres, 128, 128, 2, 2}, {kWres, 128, 16, 4, 1},
+    {kDirect, 16, 16}, {kDirect, 16, 32}, {kDirect, 16, 48}, {kDirect, 16, 64}, {kDirect, 16, 96},
+    {kDirect, 16, 192},
+    {kSpatial, 256, 32},
     // 20..26: the streaming shapes of 0..6 with a deeper LDS ring (more K stages in flight)
-    {128, 128}, {128, 64}, {64, 64}, {128, 32}, {64, 32}, {128, 16}, {64, 16},
-    // 27..33: the streaming shapes of 0..6, persistent over output tiles (conv_pers_kernel)
-    {128, 128}, {128, 64}, {64, 64}, {128, 32}, {64, 32}, {128, 16}, {64, 16},
-    // 34: small-K wave-streaming kernel (32-pixel wave tiles x up to 192 channels)
-    {32, 96},
-    // 35: narrow-output wave-streaming kernel (32-pixel wave tiles x <= 32 channels, full K)
-    {32, 32},
-    // 36..41: patch-resident kernel (TH x 16 M-grid pixels x BN channels, 8 waves)
-    {128, 192}, {128, 128}, {128, 96}, {128, 256}, {128, 192}, {128, 64},
-    // 42..47: fragment-streamed patch kernel (TH x 16 pixels x BN channels)
-    {128, 192}, {64, 192}, {128, 128}, {64, 128}, {128, 256}, {128, 64},
+    {kDeep, 128, 128, 2, 2, 2}, {kDeep, 128, 64, 4, 1, 2}, {kDeep, 64, 64, 2, 2, 2},
+    {kDeep, 128, 32, 4, 1, 2}, {kDeep, 64, 32, 2, 2, 3}, {kDeep, 128, 16, 4, 1, 2},
+    {kDeep, 64, 16, 4, 1, 3},
+    // 27..33: the streaming shapes of 0..6, persistent over output tiles
+    {kPers, 128, 128, 2, 2, 2}, {kPers, 128, 64, 4, 1, 3}, {kPers, 64, 64, 2, 2, 3},
+    {kPers, 128, 32, 4, 1, 3}, {kPers, 64, 32, 2, 2, 3}, {kPers, 128, 16, 4, 1, 3},
+    {kPers, 64, 16, 4, 1, 3},
+    // 34: 32-pixel wave tiles x up to 192 channels; 35: x <= 32 channels, full K
+    {kSmallK, 32, 96}, {kWStream, 32, 32},
+    // 36..41: TH x 16 M-grid pixels x BN channels, 8 waves
+    {kPatch, 128, 192, 2, 4, 3}, {kPatch, 128, 128, 2, 4, 3}, {kPatch, 128, 96, 4, 2, 3},
+    {kPatch, 128, 256, 2, 4, 3}, {kPatch, 128, 192, 2, 4, 4}, {kPatch, 128, 64, 4, 2, 3},
+    // 42..47
+    {kFPatch, 128, 192}, {kFPatch, 64, 192}, {kFPatch, 128, 128}, {kFPatch, 64, 128},
+    {kFPatch, 128, 256}, {kFPatch, 128, 64},
     // 48, 49: patch-resident kernel with a 4-deep weight ring
-    {128, 64}, {128, 128},
-    // 50: fragment-streamed patch kernel, 4 x 16 pixels x 64 channels
-    {64, 64},
-    // 51..53: fragment-streamed patch kernel, unrolled K split by kernel row (KS = 3)
-    {64, 64}, {64, 128}, {64, 192},
-    // 54: full-width pointwise kernel (32-pixel wave tiles x all 192 output channels)
-    {32, 192},
-    // 55: narrow-output patch kernel (4 x 16 pixels x <= 32 channels, K split over 8 waves)
-    {64, 32},
+    {kPatch, 128, 64, 4, 2, 4}, {kPatch, 128, 128, 2, 4, 4},
+    {kFPatch, 64, 64},
+    // 51..53
+    {kFPatchKS, 64, 64, 4, 1}, {kFPatchKS, 64, 128, 4, 1}, {kFPatchKS, 64, 192, 4},
+    // 54: 32-pixel wave tiles x all 192 output channels; 55: 4 x 16 pixels, K over 8 waves
+    {kPW, 32, 192}, {kNPatch, 64, 32},
     // 56..58: K-split fragment-patch kernel on taller tiles (TH x 16 pixels: the weight
     // panel, most of a workgroup's bytes, amortised over 2-4x the pixels)
-    {128, 64}, {128, 128}, {256, 32}};
+    {kFPatchKS, 128, 64, 4}, {kFPatchKS, 128, 128, 4}, {kFPatchKS, 256, 32, 2}};
 constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
-constexpr int kFirstWres = 7;
 constexpr int kWresStages = 6;
-constexpr int kFirstDirect = 13;   // 13..18: direct kernel with NT = bn/16
 constexpr int kDirectSteps = 12;
-constexpr int kTileSpatial = 19;   // conv3x3_c32_kernel (16x16 pixels x 32 channels)
-constexpr int kFirstDeep = 20;     // 20..26: deep-ring streaming tiles
-constexpr int kFirstPers = 27;     // 27..33: persistent streaming tiles
-constexpr int kTileSmallK = 34;    // conv_smallk_kernel (bf16, plain conv, K <= 256)
-constexpr int kTileWStream = 35;   // conv_wstream_kernel (bf16, stride 1, k 1/3, cout <= 32)
-constexpr int kFirstPatch = 36;    // 36..41: conv_patch_kernel (bf16; k3 s1 conv/subpel, convT)
-constexpr int kFirstFPatch = 42;   // 42..47: conv_fpatch_kernel (fragment-major weights)
-constexpr int kFirstPatch2 = 48;   // 48, 49: conv_patch_kernel with NBUF = 4
-constexpr int kTileFPatch464 = 50; // conv_fpatch_kernel<4, 64>
-constexpr int kFirstFPatchKS = 51; // 51..53: conv_fpatch_kernel<4, 64|128|192, ..., KS = 3>
-constexpr int kTilePW = 54;        // conv_pw_kernel (bf16 1x1, one source, cin/cout <= 192)
-constexpr int kTileNPatch = 55;    // conv_npatch_kernel (bf16 3x3 s1, cout <= 32, fragment-major)
-constexpr int kFirstFPatchKS2 = 56; // 56..58: conv_fpatch_kernel<8,64|8,128|16,32, ..., KS = 3>
-__host__ __device__ constexpr bool patch_tile(int t) {   // conv_patch_kernel tiles
-  return (t >= 36 && t <= 41) || t == 48 || t == 49;
+constexpr bool stream_tile(int t) { return kTiles[t].kind == kStream || kTiles[t].kind == kDeep; }
+constexpr bool patch_tile(int t) { return kTiles[t].kind == kPatch; }
+constexpr bool fpatch_tile(int t) {
+  return kTiles[t].kind == kFPatch || kTiles[t].kind == kFPatchKS;
 }
-__host__ __device__ constexpr bool fpatch_tile(int t) {
-  return (t >= 42 && t <= 47) || (t >= 50 && t <= 53) || (t >= 56 && t <= 58);
-}
-__host__ __device__ constexpr bool fpatch_ks_tile(int t) {
-  return (t >= 51 && t <= 53) || (t >= 56 && t <= 58);
-}
+
+// What plan_conv decides for one launch and launch_conv consumes: the tile, the inner choice
+// of the kernel instantiation, its launch geometry and its name (rocprofv3's spelling).
+struct ConvPlan {
+  int tile;
+  int v0, v1;    // pw: kernel (3 pw3 / 2 pw2 / 1 pw), NKS; smallk: NT, NKS; wstream: NW;
+                 // npatch: TN; fpatch / fpatch-ks: CPT; patch: DACT; direct: row stride
+  dim3 grid;     // smallk / pw / pers: x = the tiles to cover; the launch caps it by the CUs
+  int block;
+  size_t lds;    // dynamic LDS bytes
+  bool reduce;   // a separate split-K epilogue launch follows (unless reduced in-launch)
+  char name[96];
+};
 #ifndef RGBAC_RC1
 #define RGBAC_RC1 24   // unrolled-K fragment-patch weight ring depth at TN 1 (TN 2: half)
 #endif
@@ -1238,7 +1260,7 @@ __global__ void __launch_bounds__(256, 2) conv_smallk_kernel(const ConvArgsDev a
 }
 
 template <int NT, int NKS>
-static void launch_smallk_nt(const ConvArgsDev& d, int ny, int nz, hipStream_t st) {
+static void launch_smallk_nt(const ConvArgsDev& d, const ConvPlan& p, hipStream_t st) {
   static int per_cu = -1;                            // a property of the kernel
   auto kern = conv_smallk_kernel<NT, NKS>;
   if (per_cu < 0) {
@@ -1246,34 +1268,31 @@ static void launch_smallk_nt(const ConvArgsDev& d, int ny, int nz, hipStream_t s
         per_cu < 1)
       per_cu = 1;
   }
-  const int ncu = device_cus();
-  const int ntile = (d.s.M + 31) / 32;
-  int gx = (ncu * per_cu + ny * nz - 1) / (ny * nz);
-  const int need = (ntile + 3) / 4;
-  if (gx > need) gx = need;
+  const int nyz = p.grid.y * p.grid.z;
+  int gx = (device_cus() * per_cu + nyz - 1) / nyz;
+  if (gx > (int)p.grid.x) gx = p.grid.x;
   if (gx < 1) gx = 1;
-  hipLaunchKernelGGL(kern, dim3(gx, ny, nz), dim3(256), 0, st, d);
+  hipLaunchKernelGGL(kern, dim3(gx, p.grid.y, p.grid.z), dim3(256), 0, st, d);
 }
 
 template <int NKS>
-static void launch_smallk_k(const ConvArgsDev& d, int max_cout, hipStream_t st) {
-  const int nz = d.s.ngroups;
-  if (max_cout <= 32) launch_smallk_nt<1, NKS>(d, 1, nz, st);
-  else if (max_cout <= 64) launch_smallk_nt<2, NKS>(d, 1, nz, st);
-  else launch_smallk_nt<3, NKS>(d, (max_cout + 95) / 96, nz, st);
+static void launch_smallk_k(const ConvArgsDev& d, const ConvPlan& p, hipStream_t st) {
+  if (p.v0 == 1) launch_smallk_nt<1, NKS>(d, p, st);
+  else if (p.v0 == 2) launch_smallk_nt<2, NKS>(d, p, st);
+  else launch_smallk_nt<3, NKS>(d, p, st);
 }
 
-static void launch_smallk(const ConvArgsDev& d, int nks16, int max_cout, hipStream_t st) {
-  switch (nks16) {
-    case 1: launch_smallk_k<1>(d, max_cout, st); break;
-    case 2: launch_smallk_k<2>(d, max_cout, st); break;
-    case 3: launch_smallk_k<3>(d, max_cout, st); break;
-    case 4: launch_smallk_k<4>(d, max_cout, st); break;
-    case 5: launch_smallk_k<5>(d, max_cout, st); break;
-    case 6: launch_smallk_k<6>(d, max_cout, st); break;
-    case 7: case 8: launch_smallk_k<8>(d, max_cout, st); break;
-    case 9: case 10: case 11: case 12: launch_smallk_k<12>(d, max_cout, st); break;
-    default: launch_smallk_k<16>(d, max_cout, st); break;
+static void launch_smallk(const ConvArgsDev& d, const ConvPlan& p, hipStream_t st) {
+  switch (p.v1) {
+    case 1: launch_smallk_k<1>(d, p, st); break;
+    case 2: launch_smallk_k<2>(d, p, st); break;
+    case 3: launch_smallk_k<3>(d, p, st); break;
+    case 4: launch_smallk_k<4>(d, p, st); break;
+    case 5: launch_smallk_k<5>(d, p, st); break;
+    case 6: launch_smallk_k<6>(d, p, st); break;
+    case 8: launch_smallk_k<8>(d, p, st); break;
+    case 12: launch_smallk_k<12>(d, p, st); break;
+    default: launch_smallk_k<16>(d, p, st); break;
   }
 }
 
@@ -1651,35 +1670,27 @@ __global__ void __launch_bounds__(512, 2) conv_pw2_kernel(const ConvArgsDev args
 // DACT: the instance with the folded activation backward (training input gradients); the
 // forward's instance leaves that epilogue out (the kernel sits at its 128-VGPR limit)
 template <int NKS, bool DACT>
-static void launch_pw_k(const ConvArgsDev& d, hipStream_t st) {
+static void launch_pw_k(const ConvArgsDev& d, const ConvPlan& p, hipStream_t st) {
   auto kern = conv_pw_kernel<NKS, DACT>;
-  constexpr size_t lds = (size_t)192 * 4 * NKS * 16;
   static unsigned long long attr = 0;                 // per device
-  lds_optin((const void*)kern, (int)lds, &attr);
-  const int ncu = device_cus();
-  const int nz = d.s.ngroups;
-  const int ntile = (d.s.M + 15) / 16;
-  int gx = (2 * ncu + nz - 1) / nz;
-  const int need = (ntile + 7) / 8;
-  if (gx > need) gx = need;
+  lds_optin((const void*)kern, (int)p.lds, &attr);
+  const int nz = p.grid.z;
+  int gx = (2 * device_cus() + nz - 1) / nz;
+  if (gx > (int)p.grid.x) gx = p.grid.x;
   if (gx < 1) gx = 1;
-  hipLaunchKernelGGL(kern, dim3(gx, 1, nz), dim3(512), lds, st, d);
+  hipLaunchKernelGGL(kern, dim3(gx, 1, nz), dim3(512), p.lds, st, d);
 }
 
 template <int NKS>
-static void launch_pw2_k(const ConvArgsDev& d, hipStream_t st) {
+static void launch_pw2_k(const ConvArgsDev& d, const ConvPlan& p, hipStream_t st) {
   auto kern = conv_pw2_kernel<NKS>;
-  constexpr size_t lds = ((size_t)192 * 4 * NKS + 8 * 16 * 24) * 16;
   static unsigned long long attr = 0;                 // per device
-  lds_optin((const void*)kern, (int)lds, &attr);
-  const int ncu = device_cus();
-  const int nz = d.s.ngroups;
-  const int ntile = (d.s.M + 15) / 16;
-  int gx = (ncu + nz - 1) / nz;
-  const int need = (ntile + 7) / 8;
-  if (gx > need) gx = need;
+  lds_optin((const void*)kern, (int)p.lds, &attr);
+  const int nz = p.grid.z;
+  int gx = (device_cus() + nz - 1) / nz;
+  if (gx > (int)p.grid.x) gx = p.grid.x;
   if (gx < 1) gx = 1;
-  hipLaunchKernelGGL(kern, dim3(gx, 1, nz), dim3(512), lds, st, d);
+  hipLaunchKernelGGL(kern, dim3(gx, 1, nz), dim3(512), p.lds, st, d);
 }
 
 // conv_pw2_kernel's preconditions (the rest -- one source, 1x1, cin/cout <= 192 -- are the
@@ -1708,26 +1719,22 @@ static bool pw2_ok(const ConvArgsDev& d) {
   return true;
 }
 
-static void launch_pw(const ConvArgsDev& d, int cin_max, hipStream_t st) {
-  if (pw3_ok(d, cin_max)) {                        // GDN / IGDN forward: pw3.hip
+static void launch_pw(const ConvArgsDev& d, const ConvPlan& p, hipStream_t st) {
+  if (p.v0 == 3) {                                 // GDN / IGDN forward: pw3.hip
     launch_pw3(d, st);
-    return;
+  } else if (p.v0 == 2) {
+    if (p.v1 == 2) launch_pw2_k<2>(d, p, st);
+    else if (p.v1 == 4) launch_pw2_k<4>(d, p, st);
+    else launch_pw2_k<6>(d, p, st);
+  } else if (is_dact(d.s.act)) {
+    if (p.v1 == 2) launch_pw_k<2, true>(d, p, st);
+    else if (p.v1 == 4) launch_pw_k<4, true>(d, p, st);
+    else launch_pw_k<6, true>(d, p, st);
+  } else {
+    if (p.v1 == 2) launch_pw_k<2, false>(d, p, st);
+    else if (p.v1 == 4) launch_pw_k<4, false>(d, p, st);
+    else launch_pw_k<6, false>(d, p, st);
   }
-  if (pw2_ok(d)) {
-    if (cin_max <= 64) launch_pw2_k<2>(d, st);
-    else if (cin_max <= 128) launch_pw2_k<4>(d, st);
-    else launch_pw2_k<6>(d, st);
-    return;
-  }
-  if (is_dact(d.s.act)) {
-    if (cin_max <= 64) launch_pw_k<2, true>(d, st);
-    else if (cin_max <= 128) launch_pw_k<4, true>(d, st);
-    else launch_pw_k<6, true>(d, st);
-    return;
-  }
-  if (cin_max <= 64) launch_pw_k<2, false>(d, st);
-  else if (cin_max <= 128) launch_pw_k<4, false>(d, st);
-  else launch_pw_k<6, false>(d, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -1939,20 +1946,13 @@ __global__ void __launch_bounds__(512) conv_npatch_kernel(const ConvArgsDev args
   WG_T(3);
 }
 
-static void launch_npatch(const ConvArgsDev& d, int max_cout, hipStream_t st) {
-  int cmax = 0;
-  for (int i = 0; i < d.s.ngroups; ++i) cmax = d.g[i].cin_pad > cmax ? d.g[i].cin_pad : cmax;
-  const size_t patch = (size_t)6 * 18 * (((cmax + 31) & ~31) / 8 + 2) * 16;
-  const int tn = max_cout > 16 ? 2 : 1;
-  const size_t red = (size_t)8 * tn * 4 * 64 * 16;
-  const size_t lds = ((patch > red ? patch : red) + 1023) & ~(size_t)1023;
-  const dim3 grid((unsigned)((long long)d.s.batch * (d.s.Hm / 4) * (d.s.Wm / 16)), 1, d.s.ngroups);
+static void launch_npatch(const ConvArgsDev& d, const ConvPlan& p, hipStream_t st) {
   // (below 160 KiB: the kernel also holds a few static LDS words); per device
   static unsigned long long attr1 = 0, attr2 = 0;
   lds_optin((const void*)conv_npatch_kernel<1>, 128 * 1024, &attr1);
   lds_optin((const void*)conv_npatch_kernel<2>, 128 * 1024, &attr2);
-  if (tn == 2) hipLaunchKernelGGL(conv_npatch_kernel<2>, grid, dim3(512), lds, st, d);
-  else hipLaunchKernelGGL(conv_npatch_kernel<1>, grid, dim3(512), lds, st, d);
+  if (p.v0 == 2) hipLaunchKernelGGL(conv_npatch_kernel<2>, p.grid, dim3(512), p.lds, st, d);
+  else hipLaunchKernelGGL(conv_npatch_kernel<1>, p.grid, dim3(512), p.lds, st, d);
 }
 
 // ---------------------------------------------------------------------------
@@ -2110,24 +2110,9 @@ __global__ void __launch_bounds__(64 * NW) conv_wstream_kernel(const ConvArgsDev
   WG_T(3);
 }
 
-// 8 waves split K when every wave still gets >= 8 k-steps (the latency-bound chain convs:
-// K = 2304 / 1152 -> 18 / 9 steps per wave instead of 36 / 18).
-static void launch_wstream(const ConvArgsDev& d, hipStream_t st) {
-  const int ntile = (d.s.M + 31) / 32;
-  int nks = 0;
-  for (int i = 0; i < d.s.ngroups; ++i) {
-    const int n = (d.s.ksize * d.s.ksize * d.g[i].cin_pad + 15) / 16;
-    if (n > nks) nks = n;
-  }
-  static const int nw_env = [] {
-    const char* e = getenv("RGBAC_WSTREAM_WAVES");
-    return e ? atoi(e) : 0;
-  }();
-  const int nw = nw_env == 4 || nw_env == 8 ? nw_env : (nks >= 64 ? 8 : 4);
-  if (nw == 8)
-    hipLaunchKernelGGL((conv_wstream_kernel<8, 8>), dim3(ntile, 1, d.s.ngroups), dim3(512), 0, st, d);
-  else
-    hipLaunchKernelGGL((conv_wstream_kernel<8, 4>), dim3(ntile, 1, d.s.ngroups), dim3(256), 0, st, d);
+static void launch_wstream(const ConvArgsDev& d, const ConvPlan& p, hipStream_t st) {
+  if (p.v0 == 8) hipLaunchKernelGGL((conv_wstream_kernel<8, 8>), p.grid, dim3(512), 0, st, d);
+  else hipLaunchKernelGGL((conv_wstream_kernel<8, 4>), p.grid, dim3(256), 0, st, d);
 }
 
 // Persistent grid: as many blocks per z-slice as fit on the chip at once (occupancy query,
@@ -2813,290 +2798,87 @@ _Pragma("unroll")                                                               
 #undef FP_LOAD
 }
 
-template <typename T>
-static int launch_conv(const ConvArgsDev& d, int tile, int max_cout, hipStream_t st, int part) {
-  const ConvShared& s = d.s;
-  const TileCfg tc = kTiles[tile];
-  const bool inlaunch = s.ksplit > 1 && d.g[0].cnt != nullptr &&
-                        (tile < kFirstWres || (tile >= kFirstDeep && tile < kFirstPers));
-  if (part == 2) {                         // split-K reduce + epilogue kernels only
-    const bool patch_slabs = patch_tile(tile) && s.mode == RGBAC_CONV;   // strided-conv split
-    if (s.ksplit == 1 || inlaunch || tile == kTileSpatial || tile == kTileSmallK ||
-        tile == kTileWStream || (tile >= kFirstPatch && !patch_slabs) ||
-        (tile >= kFirstWres && tile < kFirstDeep))
-      return RGBAC_OK;
-    goto splitk_epilogue;
-  }
-  if (tile == kTileSpatial) {
-    if constexpr (sizeof(T) == 2) {
-      dim3 grid((unsigned)((long long)s.batch * (s.Hm / 16) * (s.Wm / 16)), 1, s.ngroups);
-      hipLaunchKernelGGL(conv3x3_c32_kernel<T>, grid, dim3(256), 0, st, d);
-      return check_launch("conv3x3_c32_kernel");
-    } else {
-      set_error("the spatial 3x3 tile is bf16 only");
-      return RGBAC_E_ARG;
-    }
-  }
-  if (tile >= kFirstDirect && tile < kFirstDeep) {
-    const int ny = (max_cout + tc.bn - 1) / tc.bn;
-    const int nz = s.ngroups;
-    const int ntile = (s.M + 15) / 16;
-    int gx = (512 + ny * nz - 1) / (ny * nz);
-    if (gx > (ntile + 3) / 4) gx = (ntile + 3) / 4;
-    if (gx < 1) gx = 1;
-    int nks_max = 0;
-    const int kstep = sizeof(T) == 4 ? 16 : 32;
-    for (int i = 0; i < s.ngroups; ++i) {
-      const int nk = (s.ksize * s.ksize * d.g[i].cin_pad + kstep - 1) / kstep;
-      if (nk > nks_max) nks_max = nk;
-    }
-    const int rs = nks_max * 4 + 1;
-    if ((size_t)tc.bn * rs * 16 > 65536) {
-      set_error("direct tile weight panel exceeds 64 KiB of LDS");
-      return RGBAC_E_ARG;
-    }
-    dim3 grid(gx, ny, nz);
-    switch (tc.bn / 16) {
-      case 1: launch_direct<T, 1>(d, grid, rs, nks_max, st); break;
-      case 2: launch_direct<T, 2>(d, grid, rs, nks_max, st); break;
-      case 3: launch_direct<T, 3>(d, grid, rs, nks_max, st); break;
-      case 4: launch_direct<T, 4>(d, grid, rs, nks_max, st); break;
-      case 6: launch_direct<T, 6>(d, grid, rs, nks_max, st); break;
-      default: launch_direct<T, 12>(d, grid, rs, nks_max, st); break;
-    }
-    return check_launch("conv_direct_kernel");
-  }
-  if (tile >= kFirstWres && tile < kFirstDeep) {
-    const int mtiles = (s.M + tc.bm - 1) / tc.bm;
-    const int ny = (max_cout + tc.bn - 1) / tc.bn;
-    const int nz = s.nphase * s.ngroups;
-    int gx = (512 + ny * nz - 1) / (ny * nz);
-    if (gx > mtiles) gx = mtiles;
-    if (gx < 1) gx = 1;
-    dim3 grid(gx, ny, nz);
-    constexpr int NS = kWresStages;
-    switch (tile) {
-      case 7: hipLaunchKernelGGL((conv_wres_kernel<T, 128, 64, 2, 2, NS>), grid, dim3(256), 0, st, d); break;
-      case 8: hipLaunchKernelGGL((conv_wres_kernel<T, 64, 64, 2, 2, NS>), grid, dim3(256), 0, st, d); break;
-      case 9: hipLaunchKernelGGL((conv_wres_kernel<T, 128, 32, 4, 1, NS>), grid, dim3(256), 0, st, d); break;
-      case 10: hipLaunchKernelGGL((conv_wres_kernel<T, 64, 32, 2, 2, NS>), grid, dim3(256), 0, st, d); break;
-      case 11: hipLaunchKernelGGL((conv_wres_kernel<T, 128, 128, 2, 2, NS>), grid, dim3(256), 0, st, d); break;
-      default: hipLaunchKernelGGL((conv_wres_kernel<T, 128, 16, 4, 1, NS>), grid, dim3(256), 0, st, d); break;
-    }
-    return check_launch("conv_wres_kernel");
-  }
-  if (tile == kTileNPatch) {
-    if constexpr (sizeof(T) == 2) {
-      launch_npatch(d, max_cout, st);
-      return check_launch("conv_npatch_kernel");
-    } else {
-      set_error("the narrow patch tile is bf16 only");
-      return RGBAC_E_ARG;
-    }
-  }
-  if (tile == kTilePW) {
-    if constexpr (sizeof(T) == 2) {
-      int cmax = 0;
-      for (int i = 0; i < s.ngroups; ++i) cmax = d.g[i].cin_pad > cmax ? d.g[i].cin_pad : cmax;
-      launch_pw(d, cmax, st);
-      return check_launch("conv_pw_kernel");
-    } else {
-      set_error("the full-width pointwise tile is bf16 only");
-      return RGBAC_E_ARG;
-    }
-  }
-  if (fpatch_tile(tile)) {
-    if constexpr (sizeof(T) == 2) {
-      const int th = tc.bm / 16;
-      const int nbn = (max_cout + tc.bn - 1) / tc.bn;
-      const long long nsp = (long long)s.batch * (s.Hm / th) * (s.Wm / 16) * s.ngroups;
-      int cmax = 0;
-      for (int i = 0; i < s.ngroups; ++i) cmax = d.g[i].cin_pad > cmax ? d.g[i].cin_pad : cmax;
-      size_t lds = ((size_t)(th + 2) * 18 * (((cmax + 31) & ~31) / 8 + 2) * 16 + 1023) &
-                   ~(size_t)1023;                         // whole 1-KiB DMA pieces
-      const bool ks3 = fpatch_ks_tile(tile);
-      if (ks3) {                                          // row partials over the patch
-        const size_t red = (size_t)2 * (tc.bn / 16) * th * 64 * 16;
-        if (red > lds) lds = red;
-      }
-      if (lds > 160 * 1024) {
-        set_error("fragment-patch tile: the input patch exceeds 160 KiB of LDS");
-        return RGBAC_E_ARG;
-      }
-      dim3 grid((unsigned)nsp, (unsigned)nbn, 1);
-      // the unrolled-K variant when it is a conv and every group has the same cin32 of 3, 4
-      // or 7 k-steps per tap (the slice stacks: 80..128 and 224 input channels)
-      int cpt = 0;
-      if (s.mode == RGBAC_CONV || (ks3 && s.mode == RGBAC_SUBPEL2)) {
-        cpt = ((d.g[0].cin_pad + 31) & ~31) >> 5;
-        for (int i = 1; i < s.ngroups; ++i)
-          if ((((d.g[i].cin_pad + 31) & ~31) >> 5) != cpt) cpt = 0;
-        // 8..10 k-steps per tap (the hyperprior's 256..320-channel 3x3 convs / subpel convs
-        // on the 16x16 grid): the K-split tiles 51 / 52 only
-        const bool wide = ks3 && (tile == kFirstFPatchKS || tile == kFirstFPatchKS + 1);
-        if (!(cpt == 3 || cpt == 4 || cpt == 7 || (wide && cpt >= 8 && cpt <= 10))) cpt = 0;
-        if (!fpatch_cpt_enabled()) cpt = 0;
-      }
-      if (ks3 && cpt == 0) {
-        set_error("K-split fragment-patch tiles: 3x3 conv with 96/128/224 (tiles 51/52 also "
-                  "256/288/320)-channel inputs only");
-        return RGBAC_E_ARG;
-      }
-#define RGBAC_FP1(TH_, BN_, C_)                                                               \
-  do {                                                                                        \
-    auto k_ = conv_fpatch_kernel<TH_, BN_, 4, 4, C_>;                                         \
-    static unsigned long long attr_ = 0;                                                      \
-    lds_optin((const void*)k_, 160 * 1024, &attr_);                                          \
-    hipLaunchKernelGGL(k_, grid, dim3(256), lds, st, d);                                      \
-  } while (0)
-#define RGBAC_FPK(TH_, BN_, NW_, C_)                                                          \
-  do {                                                                                        \
-    auto k_ = conv_fpatch_kernel<TH_, BN_, NW_, 4, C_, 3>;                                    \
-    static unsigned long long attr_ = 0;                                                      \
-    lds_optin((const void*)k_, 160 * 1024, &attr_);                                          \
-    hipLaunchKernelGGL(k_, grid, dim3(64 * NW_ * 3), lds, st, d);                             \
-  } while (0)
-#define RGBAC_FPKS(TH_, BN_, NW_)                                                             \
-  do {                                                                                        \
-    if (cpt == 3) RGBAC_FPK(TH_, BN_, NW_, 3);                                                \
-    else if (cpt == 4) RGBAC_FPK(TH_, BN_, NW_, 4);                                           \
-    else RGBAC_FPK(TH_, BN_, NW_, 7);                                                         \
-  } while (0)
-#define RGBAC_FPKW(BN_)                                                                       \
-  do {                                                                                        \
-    if (cpt == 8) RGBAC_FPK(4, BN_, 4, 8);                                                    \
-    else if (cpt == 9) RGBAC_FPK(4, BN_, 4, 9);                                               \
-    else if (cpt == 10) RGBAC_FPK(4, BN_, 4, 10);                                             \
-    else RGBAC_FPKS(4, BN_, 4);                                                               \
-  } while (0)
-#define RGBAC_FP(TH_, BN_)                                                                    \
-  do {                                                                                        \
-    if (TH_ != 4) RGBAC_FP1(TH_, BN_, 0);  /* 8-row tiles: the generic loop is faster */     \
-    else if (cpt == 3) RGBAC_FP1(TH_, BN_, 3);                                                \
-    else if (cpt == 4) RGBAC_FP1(TH_, BN_, 4);                                                \
-    else if (cpt == 7) RGBAC_FP1(TH_, BN_, 7);                                                \
-    else RGBAC_FP1(TH_, BN_, 0);                                                              \
-  } while (0)
-      switch (tile) {
-        case 42: RGBAC_FP(8, 192); break;
-        case 43: RGBAC_FP(4, 192); break;
-        case 44: RGBAC_FP(8, 128); break;
-        case 45: RGBAC_FP(4, 128); break;
-        case 46: RGBAC_FP(8, 256); break;
-        case kTileFPatch464: RGBAC_FP(4, 64); break;
-        case kFirstFPatchKS: RGBAC_FPKW(64); break;
-        case kFirstFPatchKS + 1: RGBAC_FPKW(128); break;
-        case kFirstFPatchKS + 2: RGBAC_FPKS(4, 192, 4); break;
-        case kFirstFPatchKS2: RGBAC_FPKS(8, 64, 4); break;
-        case kFirstFPatchKS2 + 1: RGBAC_FPKS(8, 128, 4); break;
-        case kFirstFPatchKS2 + 2: RGBAC_FPKS(16, 32, 2); break;
-        default: RGBAC_FP(8, 64); break;
-      }
-#undef RGBAC_FP
-#undef RGBAC_FP1
-#undef RGBAC_FPKW
-#undef RGBAC_FPKS
-#undef RGBAC_FPK
-      return check_launch("conv_fpatch_kernel");
-    } else {
-      set_error("the fragment-patch tiles are bf16 only");
-      return RGBAC_E_ARG;
-    }
-  }
-  if (tile >= kFirstPatch) {
-    if constexpr (sizeof(T) == 2) {
-      const int th = tc.bm / 16;
-      const long long nsp = (long long)s.batch * (s.Hm / th) * (s.Wm / 16) * s.ngroups;
-      // ksplit 4: the phase split (grid z = the 5x5/s2 conv's / convT's four phases)
-      dim3 grid((unsigned)nsp, (unsigned)((max_cout + tc.bn - 1) / tc.bn), s.ksplit > 1 ? 4 : 1);
+template <int TH, int BN, int NW, int CPT, int KS>
+static void launch_fpatch(const ConvArgsDev& d, const ConvPlan& p, hipStream_t st) {
+  auto kern = conv_fpatch_kernel<TH, BN, NW, 4, CPT, KS>;
+  static unsigned long long attr = 0;                 // per device
+  lds_optin((const void*)kern, 160 * 1024, &attr);
+  hipLaunchKernelGGL(kern, p.grid, dim3(p.block), p.lds, st, d);
+}
+
+// The main kernel of tile TILE, its template arguments read from kTiles[TILE]; the inner
+// choices (ConvPlan::v0 / v1) select among the instantiations of that tile.
+template <typename T, int TILE>
+static void launch_tile(const ConvArgsDev& d, const ConvPlan& p, hipStream_t st) {
+  constexpr TileDesc t = kTiles[TILE];
+  constexpr int TH = t.bm / 16;
+  if constexpr (t.kind == kStream || t.kind == kDeep) {
+    hipLaunchKernelGGL((conv_kernel<T, t.bm, t.bn, t.a, t.b, t.c, t.kind == kDeep ? 2 : 1>),
+                       p.grid, dim3(256), 0, st, d);
+  } else if constexpr (t.kind == kPers) {
+    launch_pers<T, t.bm, t.bn, t.a, t.b, t.c>(d, p.grid.x, p.grid.z, st);
+  } else if constexpr (t.kind == kWres) {
+    hipLaunchKernelGGL((conv_wres_kernel<T, t.bm, t.bn, t.a, t.b, kWresStages>), p.grid,
+                       dim3(256), 0, st, d);
+  } else if constexpr (t.kind == kDirect) {
+    launch_direct<T, t.bn / 16>(d, p.grid, p.v0, st);
+  } else if constexpr (sizeof(T) == 2) {           // every other kind is bf16 only (plan_conv)
+    if constexpr (t.kind == kSpatial) {
+      hipLaunchKernelGGL(conv3x3_c32_kernel<T>, p.grid, dim3(256), 0, st, d);
+    } else if constexpr (t.kind == kSmallK) {
+      launch_smallk(d, p, st);
+    } else if constexpr (t.kind == kWStream) {
+      launch_wstream(d, p, st);
+    } else if constexpr (t.kind == kPW) {
+      launch_pw(d, p, st);
+    } else if constexpr (t.kind == kNPatch) {
+      launch_npatch(d, p, st);
+    } else if constexpr (t.kind == kPatch) {
       // the folded activation backward (training input gradients) in instances of their own:
       // the forward instances keep the register allocation they were tuned with (the shared
       // epilogue code cost the 5x5/s2 patch kernels 37 % when compiled into them)
-#define PATCH_LAUNCH(DA)                                                                               \
-      switch (tile) {                                                                                  \
-        case 36: hipLaunchKernelGGL((conv_patch_kernel<8, 192, 2, 4, 3, DA>), grid, dim3(512), 0, st, d); break; \
-        case 37: hipLaunchKernelGGL((conv_patch_kernel<8, 128, 2, 4, 3, DA>), grid, dim3(512), 0, st, d); break; \
-        case 38: hipLaunchKernelGGL((conv_patch_kernel<8, 96, 4, 2, 3, DA>), grid, dim3(512), 0, st, d); break;  \
-        case 39: hipLaunchKernelGGL((conv_patch_kernel<8, 256, 2, 4, 3, DA>), grid, dim3(512), 0, st, d); break; \
-        case 40: hipLaunchKernelGGL((conv_patch_kernel<8, 192, 2, 4, 4, DA>), grid, dim3(512), 0, st, d); break; \
-        case 48: hipLaunchKernelGGL((conv_patch_kernel<8, 64, 4, 2, 4, DA>), grid, dim3(512), 0, st, d); break;  \
-        case 49: hipLaunchKernelGGL((conv_patch_kernel<8, 128, 2, 4, 4, DA>), grid, dim3(512), 0, st, d); break; \
-        default: hipLaunchKernelGGL((conv_patch_kernel<8, 64, 4, 2, 3, DA>), grid, dim3(512), 0, st, d); break;  \
-      }
-      if (is_dact(s.act)) {
-        PATCH_LAUNCH(true)
-      } else {
-        PATCH_LAUNCH(false)
-      }
-#undef PATCH_LAUNCH
-      const int rc = check_launch("conv_patch_kernel");
-      if (rc || s.ksplit == 1 || s.mode != RGBAC_CONV || part == 1) return rc;
-      goto splitk_epilogue;
+      if (p.v0)
+        hipLaunchKernelGGL((conv_patch_kernel<TH, t.bn, t.a, t.b, t.c, true>), p.grid, dim3(512),
+                           0, st, d);
+      else
+        hipLaunchKernelGGL((conv_patch_kernel<TH, t.bn, t.a, t.b, t.c, false>), p.grid, dim3(512),
+                           0, st, d);
+    } else if constexpr (t.kind == kFPatch) {
+      if (p.v0 == 3) launch_fpatch<TH, t.bn, 4, 3, 1>(d, p, st);
+      else if (p.v0 == 4) launch_fpatch<TH, t.bn, 4, 4, 1>(d, p, st);
+      else if (p.v0 == 7) launch_fpatch<TH, t.bn, 4, 7, 1>(d, p, st);
+      else launch_fpatch<TH, t.bn, 4, 0, 1>(d, p, st);
     } else {
-      set_error("the patch tiles are bf16 only");
-      return RGBAC_E_ARG;
-    }
-  }
-  if (tile == kTileWStream) {
-    if constexpr (sizeof(T) == 2) {
-      launch_wstream(d, st);
-      return check_launch("conv_wstream_kernel");
-    } else {
-      set_error("the narrow wave-streaming tile is bf16 only");
-      return RGBAC_E_ARG;
-    }
-  }
-  if (tile == kTileSmallK) {
-    if constexpr (sizeof(T) == 2) {
-      int nks16 = 0;
-      for (int i = 0; i < s.ngroups; ++i) {
-        const int k = (s.ksize * s.ksize * d.g[i].cin_pad + 15) / 16;
-        if (k > nks16) nks16 = k;
+      static_assert(t.kind == kFPatchKS, "unknown tile kind");
+      if constexpr (t.b != 0) {
+        if (p.v0 == 8) return launch_fpatch<TH, t.bn, t.a, 8, 3>(d, p, st);
+        if (p.v0 == 9) return launch_fpatch<TH, t.bn, t.a, 9, 3>(d, p, st);
+        if (p.v0 == 10) return launch_fpatch<TH, t.bn, t.a, 10, 3>(d, p, st);
       }
-      launch_smallk(d, nks16, max_cout, st);
-      return check_launch("conv_smallk_kernel");
-    } else {
-      set_error("the small-K tile is bf16 only");
-      return RGBAC_E_ARG;
+      if (p.v0 == 3) launch_fpatch<TH, t.bn, t.a, 3, 3>(d, p, st);
+      else if (p.v0 == 4) launch_fpatch<TH, t.bn, t.a, 4, 3>(d, p, st);
+      else launch_fpatch<TH, t.bn, t.a, 7, 3>(d, p, st);
     }
   }
-  if (tile >= kFirstPers) {
-    const int ntile = ((s.M + tc.bm - 1) / tc.bm) * ((max_cout + tc.bn - 1) / tc.bn);
-    const int nz = s.nphase * s.ksplit * s.ngroups;
-    switch (tile) {
-      case 27: launch_pers<T, 128, 128, 2, 2, 2>(d, ntile, nz, st); break;
-      case 28: launch_pers<T, 128, 64, 4, 1, 3>(d, ntile, nz, st); break;
-      case 29: launch_pers<T, 64, 64, 2, 2, 3>(d, ntile, nz, st); break;
-      case 30: launch_pers<T, 128, 32, 4, 1, 3>(d, ntile, nz, st); break;
-      case 31: launch_pers<T, 64, 32, 2, 2, 3>(d, ntile, nz, st); break;
-      case 32: launch_pers<T, 128, 16, 4, 1, 3>(d, ntile, nz, st); break;
-      default: launch_pers<T, 64, 16, 4, 1, 3>(d, ntile, nz, st); break;
-    }
-  } else {
-  dim3 grid((s.M + tc.bm - 1) / tc.bm, (max_cout + tc.bn - 1) / tc.bn,
-            s.nphase * s.ksplit * s.ngroups);
-  switch (tile) {
-    case 0: hipLaunchKernelGGL((conv_kernel<T, 128, 128, 2, 2, 2>), grid, dim3(256), 0, st, d); break;
-    case 1: hipLaunchKernelGGL((conv_kernel<T, 128, 64, 4, 1, 3>), grid, dim3(256), 0, st, d); break;
-    case 2: hipLaunchKernelGGL((conv_kernel<T, 64, 64, 2, 2, 3>), grid, dim3(256), 0, st, d); break;
-    case 3: hipLaunchKernelGGL((conv_kernel<T, 128, 32, 4, 1, 3>), grid, dim3(256), 0, st, d); break;
-    case 4: hipLaunchKernelGGL((conv_kernel<T, 64, 32, 2, 2, 3>), grid, dim3(256), 0, st, d); break;
-    case 5: hipLaunchKernelGGL((conv_kernel<T, 128, 16, 4, 1, 3>), grid, dim3(256), 0, st, d); break;
-    case 6: hipLaunchKernelGGL((conv_kernel<T, 64, 16, 4, 1, 3>), grid, dim3(256), 0, st, d); break;
-    case 20: hipLaunchKernelGGL((conv_kernel<T, 128, 128, 2, 2, 2, 2>), grid, dim3(256), 0, st, d); break;
-    case 21: hipLaunchKernelGGL((conv_kernel<T, 128, 64, 4, 1, 2, 2>), grid, dim3(256), 0, st, d); break;
-    case 22: hipLaunchKernelGGL((conv_kernel<T, 64, 64, 2, 2, 2, 2>), grid, dim3(256), 0, st, d); break;
-    case 23: hipLaunchKernelGGL((conv_kernel<T, 128, 32, 4, 1, 2, 2>), grid, dim3(256), 0, st, d); break;
-    case 24: hipLaunchKernelGGL((conv_kernel<T, 64, 32, 2, 2, 3, 2>), grid, dim3(256), 0, st, d); break;
-    case 25: hipLaunchKernelGGL((conv_kernel<T, 128, 16, 4, 1, 2, 2>), grid, dim3(256), 0, st, d); break;
-    default: hipLaunchKernelGGL((conv_kernel<T, 64, 16, 4, 1, 3, 2>), grid, dim3(256), 0, st, d); break;
+}
+
+template <typename T, int... I>
+static void launch_tiles(std::integer_sequence<int, I...>, const ConvArgsDev& d,
+                         const ConvPlan& p, hipStream_t st) {
+  ((p.tile == I ? launch_tile<T, I>(d, p, st) : (void)0), ...);
+}
+
+// The launch step: consumes plan_conv's decision (part: rgbac_conv2d_grouped_part).
+template <typename T>
+static int launch_conv(const ConvArgsDev& d, const ConvPlan& p, hipStream_t st, int part) {
+  const ConvShared& s = d.s;
+  if (part != 2) {
+    launch_tiles<T>(std::make_integer_sequence<int, kNumTiles>{}, d, p, st);
+    const int rc = check_launch(p.name);
+    if (rc || part == 1) return rc;
   }
-  }
-  {
-    int rc = check_launch("conv_kernel");
-    if (rc || s.ksplit == 1 || part == 1 || inlaunch) return rc;
-  }
-splitk_epilogue:
+  // split-K reduce + epilogue kernels (none when the streaming kernel reduced in-launch)
+  if (!p.reduce || (d.g[0].cnt != nullptr && stream_tile(p.tile))) return RGBAC_OK;
   for (int gi = 0; gi < s.ngroups; ++gi) {
     const long long total = (long long)s.nphase * s.M * (d.g[gi].cout16 / 4);
     long long gsz = (total + 255) / 256;
@@ -3108,10 +2890,12 @@ splitk_epilogue:
   return RGBAC_OK;
 }
 
-int fill_group(const rgbac_conv_args* a, int ntaps_max, ConvGroup& g) {
+// rgbac_conv_args -> the device-side group descriptor (validates the group).  ``buffers``:
+// also require the buffers that exist only once a choice is set (the split-K workspace).
+static int fill_group(const rgbac_conv_args* a, int ntaps_max, bool buffers, ConvGroup& g) {
   RGBAC_REQUIRE(a->nsrc >= 1 && a->nsrc <= 3, "nsrc must be 1..3");
   RGBAC_REQUIRE(a->weight && a->out, "null weight/out");
-  RGBAC_REQUIRE(a->ksplit == 1 || a->workspace ||
+  RGBAC_REQUIRE(!buffers || a->ksplit == 1 || a->workspace ||
                     (patch_tile(a->tile) && a->mode == RGBAC_CONVT_S2),   // (phase split)
                 "split-K needs a workspace");
   RGBAC_REQUIRE(a->cout > 0 && a->cout_pad % 128 == 0 && a->cout_pad >= a->cout,
@@ -3149,7 +2933,7 @@ int fill_group(const rgbac_conv_args* a, int ntaps_max, ConvGroup& g) {
                 "SQBWD needs res0 (direct gradient), res1 (x) and no bias");
   RGBAC_REQUIRE(!is_dact(a->act) || (a->res0 && !a->res1 && !a->res2 && !a->bias && !a->zout &&
                                       a->mode != RGBAC_SUBPEL2 && !a->square_input &&
-                                      !fpatch_tile(a->tile) && a->tile != kTileNPatch),
+                                      !fpatch_tile(a->tile) && kTiles[a->tile].kind != kNPatch),
                 "DGELU / DLRELU need res0 (the producer's pre-activation) and no bias, res1, res2, "
                 "zout, subpel store, squared input or fragment-major (forward-only) tile");
   g.zout = a->zout;
@@ -3176,38 +2960,16 @@ int fill_group(const rgbac_conv_args* a, int ntaps_max, ConvGroup& g) {
   return RGBAC_OK;
 }
 
-}  // namespace rgbac
+static int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
-using namespace rgbac;
-
-#ifdef RGBAC_WG_TIMING
-extern "C" int rgbac_debug_wg_times(unsigned long long* host, int nblocks) {
-  if (nblocks > 16384) nblocks = 16384;
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_wg_t), (size_t)nblocks * 4 * 8) == hipSuccess ? 0 : 1;
-}
-extern "C" int rgbac_debug_wg_reset(void) {
-  void* p = nullptr;
-  if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_wg_t)) != hipSuccess) return 1;
-  return hipMemset(p, 0, sizeof(g_wg_t)) == hipSuccess ? 0 : 1;
-}
-#endif
-
-extern "C" int rgbac_conv_num_tiles(void) { return kNumTiles; }
-// 1 for the fragment-streamed patch tiles (42..47, 50..53), whose `weight` must be the
-// fragment-major copy documented in rgbac.h; 0 for the plain packed layout; -1 out of range.
-extern "C" int rgbac_conv_tile_weight_layout(int tile) {
-  if (tile < 0 || tile >= kNumTiles) return -1;
-  return (fpatch_tile(tile) || tile == kTileNPatch) ? 1 : 0;
-}
-extern "C" int rgbac_conv_max_groups(void) { return kMaxGroups; }
-
-extern "C" int rgbac_conv2d_grouped(const rgbac_conv_args* args, int ngroups, void* stream) {
-  return rgbac_conv2d_grouped_part(args, ngroups, 0, stream);
-}
-
-extern "C" int rgbac_conv2d_grouped_part(const rgbac_conv_args* args, int ngroups, int part,
-                                         void* stream) {
-  RGBAC_REQUIRE(part >= 0 && part <= 2, "part must be 0 (all), 1 (main) or 2 (split-K epilogue)");
+// The decision step: validates (args, ngroups), fills the device-side argument block and
+// decides everything the launch needs -- which instantiation of the tile's kernel runs, its
+// grid, block, dynamic LDS and name.  Every rule about what a tile accepts and which kernel
+// it runs lives here (and in pw2_ok / pw3_ok, which it calls) and nowhere else.  It makes no
+// HIP runtime call and dereferences no pointer of ``args``, so rgbac_conv2d_grouped_describe
+// runs it in a process without a GPU; ``buffers``: see fill_group.
+static int plan_conv(const rgbac_conv_args* args, int ngroups, bool buffers, ConvArgsDev& d,
+                     ConvPlan& p) {
   RGBAC_REQUIRE(args != nullptr, "null args");
   RGBAC_REQUIRE(ngroups >= 1 && ngroups <= kMaxGroups, "ngroups must be 1..10");
   const rgbac_conv_args* a = &args[0];
@@ -3225,7 +2987,10 @@ extern "C" int rgbac_conv2d_grouped_part(const rgbac_conv_args* args, int ngroup
                       b->act_param == a->act_param && b->square_input == a->square_input,
                   "grouped convs must share geometry, tile, split and activation");
   }
-  ConvArgsDev d{};
+  const TileDesc tc = kTiles[a->tile];
+  const int th = tc.bm / 16;                     // patch kinds: tile rows
+  const bool anypatch = tc.kind == kPatch || tc.kind == kFPatch || tc.kind == kFPatchKS;
+  d = ConvArgsDev{};
   ConvShared& s = d.s;
   s.mode = a->mode;
   s.batch = a->batch;
@@ -3259,8 +3024,7 @@ extern "C" int rgbac_conv2d_grouped_part(const rgbac_conv_args* args, int ngroup
   }
   s.rWm = 1.0 / s.Wm;
   s.rHm = 1.0 / s.Hm;
-  RGBAC_REQUIRE(!(a->tile < kFirstWres || (a->tile >= kFirstDeep && a->tile < kFirstPers)) ||
-                    (long long)a->batch * a->in_h * a->in_w < (1ll << 24),
+  RGBAC_REQUIRE(!stream_tile(a->tile) || (long long)a->batch * a->in_h * a->in_w < (1ll << 24),
                 "streaming conv tiles address sources of < 2^24 pixels (24-bit gather multiply)");
   const long long M = (long long)a->batch * s.Hm * s.Wm;
   RGBAC_REQUIRE(M < (1ll << 31), "too many output pixels");
@@ -3277,7 +3041,7 @@ extern "C" int rgbac_conv2d_grouped_part(const rgbac_conv_args* args, int ngroup
     return (e && e[0] == '0') ? 0 : 1;
   }();
   s.remap = remap_env;
-  if (a->tile == kTileNPatch) {
+  if (tc.kind == kNPatch) {
     RGBAC_REQUIRE(a->dtype == RGBAC_BF16 &&
                       (a->mode == RGBAC_CONV ||
                        (a->mode == RGBAC_SUBPEL2 && !a->res0 && !a->res1 && !a->res2 &&
@@ -3298,7 +3062,7 @@ extern "C" int rgbac_conv2d_grouped_part(const rgbac_conv_args* args, int ngroup
       RGBAC_REQUIRE(a->act != RGBAC_ACT_GAUSS || args[i].cout == 16 || args[i].cout == 32,
                     "GAUSS on the narrow patch tile needs (mu|sigma) halves of 8 or 16 channels");
     }
-  } else if (a->tile == kTilePW) {
+  } else if (tc.kind == kPW) {
     RGBAC_REQUIRE(a->dtype == RGBAC_BF16 && a->mode == RGBAC_CONV && a->ksplit == 1 &&
                       a->ksize == 1 && a->stride == 1 && a->act != RGBAC_ACT_GAUSS,
                   "the full-width pointwise tile needs bf16, a 1x1 stride-1 conv, ksplit 1 and "
@@ -3306,7 +3070,7 @@ extern "C" int rgbac_conv2d_grouped_part(const rgbac_conv_args* args, int ngroup
     for (int i = 0; i < ngroups; ++i)
       RGBAC_REQUIRE(args[i].nsrc == 1 && args[i].cin_pad <= 192 && args[i].cout <= 192,
                     "the full-width pointwise tile needs one source, cin_pad <= 192, cout <= 192");
-  } else if (a->tile == kTileSpatial) {
+  } else if (tc.kind == kSpatial) {
     RGBAC_REQUIRE(a->dtype == RGBAC_BF16 && a->mode == RGBAC_CONV && a->ksize == 3 &&
                       a->stride == 1 && a->ksplit == 1 && a->act != RGBAC_ACT_GAUSS &&
                       s.Hm % 16 == 0 && s.Wm % 16 == 0,
@@ -3315,10 +3079,9 @@ extern "C" int rgbac_conv2d_grouped_part(const rgbac_conv_args* args, int ngroup
       RGBAC_REQUIRE(args[i].nsrc == 1 && args[i].cin_pad == 32 && args[i].src[0].channels == 32 &&
                         args[i].cout <= 32 && args[i].k_pad >= 288,
                     "the spatial 3x3 tile needs one 32-channel source and cout <= 32");
-  } else if (a->tile >= kFirstPatch) {
-    const int th = kTiles[a->tile].bm / 16;
+  } else if (anypatch) {
     // ksplit 4 on conv_patch_kernel tiles: the phase split of the 5x5/s2 conv / convT
-    const bool psplit = a->ksplit == 4 && patch_tile(a->tile) &&
+    const bool psplit = a->ksplit == 4 && tc.kind == kPatch &&
                         (a->mode == RGBAC_CONVT_S2 ||
                          (a->mode == RGBAC_CONV && a->ksize == 5 && a->stride == 2));
     RGBAC_REQUIRE(a->dtype == RGBAC_BF16 && (a->ksplit == 1 || psplit) && !a->square_input &&
@@ -3327,7 +3090,7 @@ extern "C" int rgbac_conv2d_grouped_part(const rgbac_conv_args* args, int ngroup
                        (a->ksize == 3 && a->stride == 1 &&
                         (a->mode == RGBAC_CONV || a->mode == RGBAC_SUBPEL2)) ||
                        (a->mode == RGBAC_CONV && a->ksize == 5 && a->stride == 2 &&
-                        !fpatch_tile(a->tile))) &&
+                        tc.kind == kPatch)) &&
                       s.Wm % 16 == 0 && s.Hm % th == 0,
                   "the patch tiles need bf16, ksplit 1, a 3x3 stride-1 conv/subpel, the 5x5/s2 "
                   "convT or (conv_patch_kernel tiles) the 5x5/s2 conv, the M grid a multiple of "
@@ -3335,13 +3098,11 @@ extern "C" int rgbac_conv2d_grouped_part(const rgbac_conv_args* args, int ngroup
     RGBAC_REQUIRE((long long)a->batch * a->in_h * a->in_w < (1ll << 24),
                   "patch tiles address sources of < 2^24 pixels");
     for (int i = 0; i < ngroups; ++i)
-      RGBAC_REQUIRE(args[i].cout_pad >= ((args[i].cout + kTiles[a->tile].bn - 1) /
-                                         kTiles[a->tile].bn) * kTiles[a->tile].bn &&
+      RGBAC_REQUIRE(args[i].cout_pad >= ceil_div(args[i].cout, tc.bn) * tc.bn &&
                         args[i].k_pad >= ntaps_max * args[i].cin_pad &&
-                        (!fpatch_tile(a->tile) ||
-                         args[i].cout_pad % 16 == 0),
+                        (tc.kind == kPatch || args[i].cout_pad % 16 == 0),
                     "patch tiles read whole BN-row weight tiles");
-  } else if (a->tile == kTileWStream) {
+  } else if (tc.kind == kWStream) {
     RGBAC_REQUIRE(a->dtype == RGBAC_BF16 && a->mode == RGBAC_CONV && a->ksplit == 1 &&
                       a->stride == 1 && (a->ksize == 1 || a->ksize == 3),
                   "the narrow wave-streaming tile needs bf16, a stride-1 1x1/3x3 conv, ksplit 1");
@@ -3353,7 +3114,7 @@ extern "C" int rgbac_conv2d_grouped_part(const rgbac_conv_args* args, int ngroup
                         (args[i].cout % 16 == 0 && args[i].cout <= 32),
                     "GAUSS on the narrow tile needs (mu|sigma) halves of 8 or 16 channels");
     }
-  } else if (a->tile == kTileSmallK) {
+  } else if (tc.kind == kSmallK) {
     RGBAC_REQUIRE(a->dtype == RGBAC_BF16 && a->mode == RGBAC_CONV && a->ksplit == 1 &&
                       a->act != RGBAC_ACT_GAUSS,
                   "the small-K tile needs bf16, a plain conv, ksplit 1 and no GAUSS epilogue");
@@ -3361,14 +3122,14 @@ extern "C" int rgbac_conv2d_grouped_part(const rgbac_conv_args* args, int ngroup
     for (int i = 0; i < ngroups; ++i)
       RGBAC_REQUIRE(args[i].cin_pad <= kSmallKMax && args[i].nsrc == 1,
                     "the small-K tile needs one source with cin_pad <= 256");
-  } else if (a->tile >= kFirstDirect && a->tile < kFirstDeep) {
+  } else if (tc.kind == kDirect) {
     RGBAC_REQUIRE(a->mode == RGBAC_CONV && a->ksplit == 1 && a->act != RGBAC_ACT_GAUSS,
                   "direct tiles need a plain conv, ksplit 1 and no GAUSS epilogue");
     const int ks_elems = a->dtype == RGBAC_F32 ? 16 : 32;
     for (int i = 0; i < ngroups; ++i)
       RGBAC_REQUIRE((ntaps_max * args[i].cin_pad + ks_elems - 1) / ks_elems <= kDirectSteps,
                     "K too large for a direct tile");
-  } else if (a->tile >= kFirstWres && a->tile < kFirstDeep) {
+  } else if (tc.kind == kWres) {
     RGBAC_REQUIRE(a->ksplit == 1 && a->act != RGBAC_ACT_GAUSS,
                   "weight-resident tiles need ksplit 1 and no GAUSS epilogue");
     const int ks_elems = a->dtype == RGBAC_F32 ? 32 : 64;
@@ -3376,7 +3137,7 @@ extern "C" int rgbac_conv2d_grouped_part(const rgbac_conv_args* args, int ngroup
       RGBAC_REQUIRE((ntaps_max * args[i].cin_pad + ks_elems - 1) / ks_elems <= kWresStages,
                     "K too large for a weight-resident tile");
   }
-  int max_cout = 0;
+  int max_cout = 0, cmax = 0;
   for (int i = 0; i < ngroups; ++i) {
     const rgbac_conv_args* b = &args[i];
     if (a->mode == RGBAC_SUBPEL2) {
@@ -3385,9 +3146,8 @@ extern "C" int rgbac_conv2d_grouped_part(const rgbac_conv_args* args, int ngroup
     }
     if (a->act == RGBAC_ACT_GAUSS) {
       RGBAC_REQUIRE(a->mode == RGBAC_CONV && a->ksplit == 1, "GAUSS needs a plain conv, ksplit 1");
-      RGBAC_REQUIRE(a->tile < kFirstPers || a->tile == kTileWStream || a->tile == kTileNPatch,
-                    "GAUSS needs a non-persistent tile");
-      RGBAC_REQUIRE(b->cout % 2 == 0 && b->cout <= kTiles[a->tile].bn,
+      RGBAC_REQUIRE(tc.kind != kPers, "GAUSS needs a non-persistent tile");
+      RGBAC_REQUIRE(b->cout % 2 == 0 && b->cout <= tc.bn,
                     "GAUSS needs (mu|sigma) channels in one N tile");
       RGBAC_REQUIRE(b->partial, "GAUSS needs a partial-sum buffer");
     }
@@ -3395,13 +3155,204 @@ extern "C" int rgbac_conv2d_grouped_part(const rgbac_conv_args* args, int ngroup
       RGBAC_REQUIRE((long long)a->batch * a->in_h * a->in_w * b->src[j].ldc *
                             (a->dtype == RGBAC_F32 ? 4 : 2) < (1ll << 31),
                     "each conv source must span < 2 GiB (32-bit gather offsets)");
-    int rc = fill_group(b, ntaps_max, d.g[i]);
+    int rc = fill_group(b, ntaps_max, buffers, d.g[i]);
     if (rc) return rc;
     if (b->cout > max_cout) max_cout = b->cout;
+    if (b->cin_pad > cmax) cmax = b->cin_pad;
   }
+
+  // ---- the kernel instantiation, its geometry and its name
+  p = ConvPlan{};
+  p.tile = a->tile;
+  p.block = 256;
+  p.reduce = s.ksplit > 1 && (stream_tile(a->tile) || tc.kind == kPers ||
+                              (tc.kind == kPatch && s.mode == RGBAC_CONV));
+  const char* dt = a->dtype == RGBAC_F32 ? "float" : "bf16_t";
+  const bool dact = is_dact(s.act);
+  const int ny = ceil_div(max_cout, tc.bn);
+  const int mtiles = ceil_div(s.M, tc.bm);
+  const int ksteps = ceil_div(ntaps_max * cmax, a->dtype == RGBAC_F32 ? 16 : 32);   // MFMA k-steps
+  const int nks16 = ceil_div(s.ksize * s.ksize * cmax, 16);
+  const size_t c32 = (size_t)((cmax + 31) & ~31);
+  const unsigned nsp = anypatch ? (unsigned)((long long)s.batch * (s.Hm / th) * (s.Wm / 16) * ngroups) : 0;
+  auto name = [&p](const char* fmt, auto... v) { snprintf(p.name, sizeof(p.name), fmt, v...); };
+  switch (tc.kind) {
+    case kStream:
+    case kDeep:
+      p.grid = dim3(mtiles, ny, s.nphase * s.ksplit * ngroups);
+      name("conv_kernel<%s, %d, %d, %d, %d, %d, %d>", dt, tc.bm, tc.bn, tc.a, tc.b, tc.c,
+           tc.kind == kDeep ? 2 : 1);
+      break;
+    case kPers:
+      p.grid = dim3(mtiles * ny, 1, s.nphase * s.ksplit * ngroups);
+      name("conv_pers_kernel<%s, %d, %d, %d, %d, %d>", dt, tc.bm, tc.bn, tc.a, tc.b, tc.c);
+      break;
+    case kWres: {
+      const int nz = s.nphase * ngroups;
+      int gx = ceil_div(512, ny * nz);
+      if (gx > mtiles) gx = mtiles;
+      p.grid = dim3(gx < 1 ? 1 : gx, ny, nz);
+      name("conv_wres_kernel<%s,%dx%d>", dt, tc.bm, tc.bn);
+      break;
+    }
+    case kDirect: {
+      const int need = ((s.M + 15) / 16 + 3) / 4;
+      int gx = ceil_div(512, ny * ngroups);
+      if (gx > need) gx = need;
+      p.v0 = ksteps * 4 + 1;                             // the weight panel's row stride
+      RGBAC_REQUIRE((size_t)tc.bn * p.v0 * 16 <= 65536,
+                    "direct tile weight panel exceeds 64 KiB of LDS");
+      p.lds = (size_t)tc.bn * p.v0 * 16;
+      p.grid = dim3(gx < 1 ? 1 : gx, ny, ngroups);
+      name("conv_direct_kernel<%s,%d>", dt, tc.bn / 16);
+      break;
+    }
+    case kSpatial:
+      p.grid = dim3((unsigned)((long long)s.batch * (s.Hm / 16) * (s.Wm / 16)), 1, ngroups);
+      name("conv3x3_c32_kernel<%s>", dt);
+      break;
+    case kSmallK:
+      p.v0 = max_cout <= 32 ? 1 : max_cout <= 64 ? 2 : 3;                 // NT: 32-row N tiles
+      p.v1 = nks16 <= 6 ? nks16 : nks16 <= 8 ? 8 : nks16 <= 12 ? 12 : 16;  // NKS
+      p.grid = dim3(((s.M + 31) / 32 + 3) / 4, p.v0 == 3 ? ceil_div(max_cout, 96) : 1, ngroups);
+      name("conv_smallk_kernel<%d, %d>", p.v0, p.v1);
+      break;
+    case kWStream: {
+      // 8 waves split K when every wave still gets >= 8 k-steps (the latency-bound chain
+      // convs: K = 2304 / 1152 -> 18 / 9 steps per wave instead of 36 / 18)
+      static const int nw_env = [] {
+        const char* e = getenv("RGBAC_WSTREAM_WAVES");
+        return e ? atoi(e) : 0;
+      }();
+      p.v0 = nw_env == 4 || nw_env == 8 ? nw_env : (nks16 >= 64 ? 8 : 4);
+      p.block = 64 * p.v0;
+      p.grid = dim3((s.M + 31) / 32, 1, ngroups);
+      name("conv_wstream_kernel<8, %d>", p.v0);
+      break;
+    }
+    case kPW:
+      // conv_pw3_kernel (pw3.hip, which also sets its own grid) where pw3_ok admits the
+      // launch, else conv_pw2_kernel where pw2_ok does, else conv_pw_kernel; NKS 32-deep
+      // k-steps held in LDS
+      p.v1 = cmax <= 64 ? 2 : cmax <= 128 ? 4 : 6;
+      p.v0 = pw3_ok(d, cmax) ? 3 : pw2_ok(d) ? 2 : 1;
+      p.block = 512;
+      p.lds = ((size_t)192 * 4 * p.v1 + (p.v0 == 2 ? 8 * 16 * 24 : 0)) * 16;
+      p.grid = dim3(((s.M + 15) / 16 + 7) / 8, 1, ngroups);
+      if (p.v0 == 3) name("conv_pw3_kernel<6, %d>", s.act);
+      else if (p.v0 == 2) name("conv_pw2_kernel<%d>", p.v1);
+      else name("conv_pw_kernel<%d, %s>", p.v1, dact ? "true" : "false");
+      break;
+    case kNPatch: {
+      p.v0 = max_cout > 16 ? 2 : 1;                                        // TN
+      const size_t patch = (size_t)6 * 18 * (c32 / 8 + 2) * 16;
+      const size_t red = (size_t)8 * p.v0 * 4 * 64 * 16;
+      p.lds = ((patch > red ? patch : red) + 1023) & ~(size_t)1023;
+      p.block = 512;
+      p.grid = dim3((unsigned)((long long)s.batch * (s.Hm / 4) * (s.Wm / 16)), 1, ngroups);
+      name("conv_npatch_kernel<%d>", p.v0);
+      break;
+    }
+    case kPatch:
+      p.v0 = dact;
+      p.block = 512;
+      // ksplit 4: the phase split (grid z = the 5x5/s2 conv's / convT's four phases)
+      p.grid = dim3(nsp, ny, s.ksplit > 1 ? 4 : 1);
+      name("conv_patch_kernel<%d, %d, %d, %d, %d, %s>", th, tc.bn, tc.a, tc.b, tc.c,
+           dact ? "true" : "false");
+      break;
+    case kFPatch:
+    case kFPatchKS: {
+      const bool ks3 = tc.kind == kFPatchKS;
+      p.lds = ((size_t)(th + 2) * 18 * (c32 / 8 + 2) * 16 + 1023) & ~(size_t)1023;   // 1-KiB DMA pieces
+      if (ks3) {                                          // row partials over the patch
+        const size_t red = (size_t)2 * (tc.bn / 16) * th * 64 * 16;
+        if (red > p.lds) p.lds = red;
+      }
+      RGBAC_REQUIRE(p.lds <= 160 * 1024,
+                    "fragment-patch tile: the input patch exceeds 160 KiB of LDS");
+      // the unrolled-K variant when it is a conv and every group has the same cin32 of 3, 4
+      // or 7 k-steps per tap (the slice stacks: 80..128 and 224 input channels); 8..10 k-steps
+      // per tap (the hyperprior's 256..320-channel 3x3 convs / subpel convs on the 16x16
+      // grid): the K-split tiles 51 / 52 only; the plain 8-row tiles: the generic loop is faster
+      int cpt = 0;
+      if ((s.mode == RGBAC_CONV || (ks3 && s.mode == RGBAC_SUBPEL2)) && fpatch_cpt_enabled() &&
+          (ks3 || th == 4)) {
+        cpt = (int)(c32 >> 5);
+        for (int i = 0; i < ngroups; ++i)
+          if ((((d.g[i].cin_pad + 31) & ~31) >> 5) != cpt) cpt = 0;
+        if (!(cpt == 3 || cpt == 4 || cpt == 7 || (ks3 && tc.b && cpt >= 8 && cpt <= 10))) cpt = 0;
+      }
+      RGBAC_REQUIRE(!ks3 || cpt != 0,
+                    "K-split fragment-patch tiles: 3x3 conv with 96/128/224 (tiles 51/52 also "
+                    "256/288/320)-channel inputs only");
+      p.v0 = cpt;
+      p.block = ks3 ? 64 * tc.a * 3 : 256;
+      p.grid = dim3(nsp, ny, 1);
+      if (ks3) name("conv_fpatch_kernel<%d, %d, %d, 4, %d, 3>", th, tc.bn, tc.a, cpt);
+      else if (cpt) name("conv_fpatch_kernel<%d, %d, 4, 4, %d>", th, tc.bn, cpt);
+      else name("conv_fpatch_kernel<%d, %d, 4, 4>", th, tc.bn);
+      break;
+    }
+  }
+  return RGBAC_OK;
+}
+
+}  // namespace rgbac
+
+using namespace rgbac;
+
+#ifdef RGBAC_WG_TIMING
+extern "C" int rgbac_debug_wg_times(unsigned long long* host, int nblocks) {
+  if (nblocks > 16384) nblocks = 16384;
+  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_wg_t), (size_t)nblocks * 4 * 8) == hipSuccess ? 0 : 1;
+}
+extern "C" int rgbac_debug_wg_reset(void) {
+  void* p = nullptr;
+  if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_wg_t)) != hipSuccess) return 1;
+  return hipMemset(p, 0, sizeof(g_wg_t)) == hipSuccess ? 0 : 1;
+}
+#endif
+
+extern "C" int rgbac_conv_num_tiles(void) { return kNumTiles; }
+extern "C" int rgbac_conv_tile_info(int tile, int* bm, int* bn, int* kind) {
+  RGBAC_REQUIRE(tile >= 0 && tile < kNumTiles, "tile index out of range");
+  if (bm) *bm = kTiles[tile].bm;
+  if (bn) *bn = kTiles[tile].bn;
+  if (kind) *kind = kTiles[tile].kind;
+  return RGBAC_OK;
+}
+// 1 for the tiles whose `weight` must be the fragment-major copy documented in rgbac.h; 0 for
+// the plain packed layout; -1 out of range.
+extern "C" int rgbac_conv_tile_weight_layout(int tile) {
+  if (tile < 0 || tile >= kNumTiles) return -1;
+  return (fpatch_tile(tile) || kTiles[tile].kind == kNPatch) ? 1 : 0;
+}
+extern "C" int rgbac_conv_max_groups(void) { return kMaxGroups; }
+
+extern "C" int rgbac_conv2d_grouped_describe(const rgbac_conv_args* args, int ngroups,
+                                             char* kernel, int cap) {
+  ConvArgsDev d;
+  ConvPlan p;
+  const int rc = plan_conv(args, ngroups, false, d, p);
+  if (rc == RGBAC_OK && kernel && cap > 0) snprintf(kernel, (size_t)cap, "%s", p.name);
+  return rc;
+}
+
+extern "C" int rgbac_conv2d_grouped(const rgbac_conv_args* args, int ngroups, void* stream) {
+  return rgbac_conv2d_grouped_part(args, ngroups, 0, stream);
+}
+
+extern "C" int rgbac_conv2d_grouped_part(const rgbac_conv_args* args, int ngroups, int part,
+                                         void* stream) {
+  RGBAC_REQUIRE(part >= 0 && part <= 2, "part must be 0 (all), 1 (main) or 2 (split-K epilogue)");
+  ConvArgsDev d;
+  ConvPlan p;
+  const int rc = plan_conv(args, ngroups, true, d, p);
+  if (rc) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (a->dtype == RGBAC_F32) return launch_conv<float>(d, a->tile, max_cout, st, part);
-  return launch_conv<bf16_t>(d, a->tile, max_cout, st, part);
+  if (args[0].dtype == RGBAC_F32) return launch_conv<float>(d, p, st, part);
+  return launch_conv<bf16_t>(d, p, st, part);
 }
 
 extern "C" int rgbac_conv2d(const rgbac_conv_args* a, void* stream) {

@@ -463,7 +463,8 @@ __device__ __forceinline__ float gauss_elem_y(const ConvGroup& g, int m, int c, 
   return fminf(fmaxf(bits, 0.0f), 50.0f);
 }
 
-// the two-deep pointwise GDN / IGDN forward (pw3.hip), dispatched by conv.hip's launch_pw
+// the two-deep pointwise GDN / IGDN forward (pw3.hip): conv.hip's plan_conv asks pw3_ok (the
+// decision: no HIP call), its launch_pw calls launch_pw3
 bool pw3_ok(const ConvArgsDev& d, int cin_max);
 void launch_pw3(const ConvArgsDev& d, hipStream_t st);
 
@@ -534,9 +535,5 @@ __device__ __forceinline__ void wait_ring(int after) {
     else wait_ring<LW, D - 1>(after);
   }
 }
-
-
-// rgbac_conv_args -> the device-side group descriptor (validates the group; conv.hip)
-int fill_group(const rgbac_conv_args* a, int ntaps_max, ConvGroup& g);
 
 }  // namespace rgbac

@@ -17,6 +17,9 @@ F32, BF16 = 0, 1
 ACT = dict(none=0, gelu=1, relu=2, lrelu=3, tanh_half=4, gate=5, gdn=6, igdn=7, masksel=8,
            gauss=9, sqbwd=10, dgelu=11, dlrelu=12)
 CONV, CONVT_S2, SUBPEL2 = 0, 1, 2
+# enum rgbac_tile_kind, in order (rgbac_conv_tile_info)
+TILE_KINDS = ("stream", "deep", "pers", "wres", "direct", "spatial", "smallk", "wstream", "patch",
+              "fpatch", "fpatch_ks", "pw", "npatch")
 
 
 class Src(ctypes.Structure):
@@ -93,8 +96,11 @@ SIGNATURES = {
     "rgbac_conv2d": [ctypes.POINTER(ConvArgs), _VP],
     "rgbac_conv_num_tiles": [],
     "rgbac_conv_tile_weight_layout": [ctypes.c_int],
+    "rgbac_conv_tile_info": [_I32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                             ctypes.POINTER(ctypes.c_int)],
     "rgbac_conv2d_grouped": [ctypes.c_void_p, _I32, _VP],
     "rgbac_conv2d_grouped_part": [ctypes.c_void_p, _I32, _I32, _VP],
+    "rgbac_conv2d_grouped_describe": [ctypes.c_void_p, _I32, ctypes.c_char_p, _I32],
     "rgbac_conv_max_groups": [],
     "rgbac_timer_create": [ctypes.POINTER(ctypes.c_void_p)],
     "rgbac_timer_record": [_VP, _VP],

@@ -107,42 +107,52 @@ def round_up(x, m):
     return (x + m - 1) // m * m
 
 
-# conv tile shapes of csrc/conv.hip (pixels x channels); index = rgbac_conv_args.tile.
-# 0..6: streaming K-ring kernel; 7..12: weight-resident persistent kernel (K <= WRES_STAGES
-# stages of 64 bf16 / 32 f32 elements, ksplit 1).
-TILES = [(128, 128), (128, 64), (64, 64), (128, 32), (64, 32), (128, 16), (64, 16),
-         (128, 64), (64, 64), (128, 32), (64, 32), (128, 128), (128, 16),
-         (16, 16), (16, 32), (16, 48), (16, 64), (16, 96), (16, 192),
-         (256, 32),
-         (128, 128), (128, 64), (64, 64), (128, 32), (64, 32), (128, 16), (64, 16),
-         (128, 128), (128, 64), (64, 64), (128, 32), (64, 32), (128, 16), (64, 16),
-         (32, 96), (32, 32),
-         (128, 192), (128, 128), (128, 96), (128, 256), (128, 192), (128, 64),
-         (128, 192), (64, 192), (128, 128), (64, 128), (128, 256), (128, 64),
-         (128, 64), (128, 128),
-         (64, 64),
-         (64, 64), (64, 128), (64, 192),
-         (32, 192),
-         (64, 32),
-         (128, 64), (128, 128), (256, 32)]
-FIRST_WRES = 7
+# The conv tiles are described in ONE place, the kTiles table of csrc/conv.hip (index =
+# rgbac_conv_args.tile); what a tile accepts and which kernel it runs is decided there too and
+# asked through rgbac_conv2d_grouped_describe (_describe below).  Read here: (bm, bn) pixels x
+# channels and the kind of every tile.
+def _tile_table():
+    lib = _lib.load()
+    out = []
+    for t in range(lib.rgbac_conv_num_tiles()):
+        v = [ctypes.c_int() for _ in range(3)]
+        _lib.call("rgbac_conv_tile_info", t, *(ctypes.byref(x) for x in v))
+        out.append((v[0].value, v[1].value, _lib.TILE_KINDS[v[2].value]))
+    return out
+
+
+_TABLE = _tile_table()
+TILES = [(bm, bn) for bm, bn, _ in _TABLE]
+
+
+def _of_kind(*kinds):
+    return tuple(t for t, row in enumerate(_TABLE) if row[2] in kinds)
+
+
+FIRST_WRES = _of_kind("wres")[0]     # weight-resident persistent kernel (K <= WRES_STAGES stages)
 WRES_STAGES = 6
-FIRST_DIRECT = 13        # 13..18: direct kernel (plain conv, K <= DIRECT_STEPS MFMA k-steps)
+FIRST_DIRECT = _of_kind("direct")[0]    # direct kernel (plain conv, K <= DIRECT_STEPS k-steps)
 DIRECT_STEPS = 12
 DIRECT_LDS = 65536       # weight panel bytes of a direct tile (dynamic LDS limit)
-TILE_SPATIAL = 19        # conv3x3_c32_kernel: 16x16-pixel tiles, 3x3 s1, Cin 32, Cout <= 32, bf16
-FIRST_DEEP = 20          # 20..26: tiles 0..6 with 256-byte K stages (KSM = 2, 2..3 in the ring)
-FIRST_PERS = 27          # 27..33: tiles 0..6, persistent over output tiles (no GAUSS epilogue)
-STREAM_TILES = (tuple(range(FIRST_WRES)) + tuple(range(FIRST_DEEP, FIRST_DEEP + 7)) +
-                tuple(range(FIRST_PERS, FIRST_PERS + 7)))
-GAUSS_TILES = tuple(range(FIRST_WRES)) + tuple(range(FIRST_DEEP, FIRST_DEEP + 7))
-TILE_SMALLK = 34         # conv_smallk_kernel: bf16 1x1 stride-1 conv, one source, cin_pad <= 256
-TILE_WSTREAM = 35        # conv_wstream_kernel: bf16 stride-1 1x1/3x3, cout <= 32, K <= 2336
-WSTREAM_MAX_STEPS = 146
-FIRST_PATCH = 36         # 36..41: conv_patch_kernel (TH x 16 M-grid tile, BN channels, 8 waves)
-PATCH_SIG = {36: (8, 192, 2, 4, 3), 37: (8, 128, 2, 4, 3), 38: (8, 96, 4, 2, 3),
-             39: (8, 256, 2, 4, 3), 40: (8, 192, 2, 4, 4), 41: (8, 64, 4, 2, 3),
-             48: (8, 64, 4, 2, 4), 49: (8, 128, 2, 4, 4)}
+TILE_SPATIAL, = _of_kind("spatial")     # conv3x3_c32_kernel: 16x16-pixel tiles, 3x3 s1, Cin 32
+FIRST_DEEP = _of_kind("deep")[0]        # the streaming tiles with 256-byte K stages
+FIRST_PERS = _of_kind("pers")[0]        # the streaming tiles, persistent over output tiles
+STREAM_TILES = _of_kind("stream", "deep", "pers")
+GAUSS_TILES = _of_kind("stream", "deep")
+TILE_SMALLK, = _of_kind("smallk")       # conv_smallk_kernel: bf16 1x1 stride-1 conv, one source
+TILE_WSTREAM, = _of_kind("wstream")     # conv_wstream_kernel: bf16 stride-1 1x1/3x3, cout <= 32
+FIRST_PATCH = _of_kind("patch")[0]
+# tile -> (TH, BN): conv_patch_kernel (TH x 16 M-grid tile, BN channels, 8 waves) and
+# conv_fpatch_kernel (fragment-major weight copy; plain and K-split variants)
+PATCH_SIG = {t: (TILES[t][0] // 16, TILES[t][1]) for t in _of_kind("patch")}
+FPATCH_SIG = {t: (TILES[t][0] // 16, TILES[t][1]) for t in _of_kind("fpatch", "fpatch_ks")}
+TILE_PW, = _of_kind("pw")               # conv_pw_kernel: bf16 1x1 stride-1 conv, cin/cout <= 192
+TILE_NPATCH, = _of_kind("npatch")       # conv_npatch_kernel: bf16 3x3 stride-1 conv, cout <= 32
+# tiles that read the fragment-major weight copy (frag_weights): forward PackedConv only
+FRAG_TILES = frozenset(t for t in range(len(TILES))
+                       if _lib.load().rgbac_conv_tile_weight_layout(t) == 1)
+PATCH = os.environ.get("RGBAC_PATCH", "1") != "0"
+_KS_NO_SUBPEL = frozenset(_of_kind("fpatch_ks")[2:])    # see _choice_valid
 
 
 def _patch_split_ok(preps):
@@ -152,43 +162,6 @@ def _patch_split_ok(preps):
     a = preps[0].a
     return (a.mode == CONVT_S2 or (a.mode == CONV and a.ksize == 5 and a.stride == 2)) and \
         a.act not in (ACT["dgelu"], ACT["dlrelu"])
-FIRST_FPATCH = 42        # 42..47: conv_fpatch_kernel (fragment-major weight copy, 4 waves)
-FPATCH_SIG = {42: (8, 192), 43: (4, 192), 44: (8, 128), 45: (4, 128), 46: (8, 256), 47: (8, 64),
-              50: (4, 64), 51: (4, 64), 52: (4, 128), 53: (4, 192),
-              56: (8, 64), 57: (8, 128), 58: (16, 32)}
-# 51..53: the unrolled-K variants with K split by kernel row (KS = 3, 12 waves): only where
-# the unrolled-K variant applies (fpatch_cpt != 0)
-FPATCH_KS = {51: 4, 52: 4, 53: 4, 56: 4, 57: 4, 58: 2}    # tile -> N waves (x 3 K parts)
-TILE_PW = 54             # conv_pw_kernel: bf16 1x1 stride-1 conv, one source, cin/cout <= 192
-TILE_NPATCH = 55         # conv_npatch_kernel: bf16 3x3 stride-1 conv, cout <= 32 (chain tails)
-# tiles that read the fragment-major weight copy (frag_weights): forward PackedConv only
-FRAG_TILES = frozenset(FPATCH_SIG) | {TILE_NPATCH}
-# the fragment-patch kernel's unrolled-K variants (csrc/conv.hip, CPT template argument)
-FPATCH_CPT = os.environ.get("RGBAC_FPATCH_CPT", "1") != "0"
-
-
-def fpatch_cpt(preps):
-    """CPT (32-deep k-steps per tap) of the unrolled-K fragment-patch variant the launcher
-    picks for these convs, or 0 for the generic loop."""
-    if not FPATCH_CPT or preps[0].pk.mode != CONV:
-        return 0
-    c = {round_up(p.pk.cin_pad, 32) // 32 for p in preps}
-    return c.pop() if len(c) == 1 and next(iter(c)) in (3, 4, 7) else 0
-def fpatch_cpt_ks(preps, tile):
-    """CPT of a K-split fragment-patch tile (51-53, 56-58) for these convs, 0 if it does not
-    apply: conv with 3 / 4 / 7 k-steps per tap, and on tiles 51 / 52 also subpel convs and
-    8..10 k-steps per tap (csrc/conv.hip launch_conv)."""
-    if not FPATCH_CPT:
-        return 0
-    wide = tile in (51, 52)
-    if preps[0].pk.mode != CONV and not (wide and preps[0].pk.mode == SUBPEL2):
-        return 0
-    c = {round_up(p.pk.cin_pad, 32) // 32 for p in preps}
-    if len(c) != 1:
-        return 0
-    c = c.pop()
-    return c if c in (3, 4, 7) or (wide and 8 <= c <= 10) else 0
-PATCH = os.environ.get("RGBAC_PATCH", "1") != "0"
 
 
 def frag_weights(pk):
@@ -219,59 +192,6 @@ def _has_frag(pk):
     return isinstance(pk, PackedConv) or getattr(pk, "frag", None) is not None
 
 
-def _patch_tiles(preps):
-    """Patch-resident tiles that apply to these (grouped) convs: bf16, the 5x5/s2 convT or a
-    3x3 stride-1 conv/subpel, no squared input / GAUSS epilogue, M grid a multiple of 16 wide
-    and of the tile height high, whole BN-row weight tiles inside the packed rows."""
-    if not PATCH:
-        return []
-    a = preps[0].a
-    if a.dtype != _lib.BF16 or a.square_input or a.act == ACT["gauss"]:
-        return []
-    s2 = a.mode == CONV and a.ksize == 5 and a.stride == 2
-    if a.mode == CONVT_S2:
-        hm, wm = a.in_h, a.in_w
-    elif a.ksize == 3 and a.stride == 1 and a.mode in (CONV, SUBPEL2):
-        hm, wm = a.in_h, a.in_w
-    elif s2:
-        # the polyphase strided conv (csrc/conv.hip conv_patch_kernel): the output grid
-        hm, wm = a.out_h, a.out_w
-    else:
-        return []
-    if wm % 16 or a.batch * a.in_h * a.in_w >= (1 << 24):
-        return []
-    out = []
-    for t, (th, bn, _, _, _) in PATCH_SIG.items():
-        if hm % th:
-            continue
-        if all(p.pk.cout_pad >= -(-p.pk.cout // bn) * bn for p in preps):
-            out.append(t)
-    # fragment-streamed tiles: PackedConv weights only (the training packs are re-gathered
-    # every step in the plain layout) and the whole patch in LDS; no strided conv
-    if not s2 and all(_has_frag(p.pk) for p in preps) and \
-            a.act not in (ACT["dgelu"], ACT["dlrelu"]):
-        c32 = max(round_up(p.pk.cin_pad, 32) for p in preps)
-        for t, (th, bn) in FPATCH_SIG.items():
-            if hm % th or (th + 2) * 18 * (c32 // 8 + 2) * 16 > 160 * 1024:
-                continue
-            if t in FPATCH_KS and 2 * (bn // 16) * th * 1024 > 160 * 1024:
-                continue
-            if t in FPATCH_KS and not fpatch_cpt_ks(preps, t):
-                continue
-            if all(p.pk.cout_pad >= -(-p.pk.cout // bn) * bn for p in preps):
-                out.append(t)
-    return out
-def _patch_cands(preps):
-    """(tile, ksplit) candidates of the patch tiles: every applicable tile unsplit, and the
-    conv_patch_kernel tiles with the phase split where it applies."""
-    ts = _patch_tiles(preps)
-    out = [(t, 1) for t in ts]
-    if _patch_split_ok(preps):
-        out += [(t, 4) for t in ts if t in PATCH_SIG]
-    return out
-
-
-SMALLK_MAX = 256
 KSPLITS = (1, 2, 4, 8)
 TUNE = os.environ.get("RGBAC_TUNE", "1") != "0"
 # RGBAC_TILE_SET: "stream" (default: streaming K-ring tiles; the weight-resident and
@@ -308,18 +228,6 @@ def side_streams(dev):
 def pick_cout_pad(cout):
     """Packed weight rows per phase: every tile's N blocks stay inside the buffer."""
     return round_up(cout, 128)
-
-
-def _wstream_ok(preps):
-    a = preps[0].a
-    if not (a.dtype == _lib.BF16 and a.mode == CONV and a.stride == 1 and a.ksize in (1, 3)):
-        return False
-    for p in preps:
-        if p.pk.cout > 32 or -(-a.ksize * a.ksize * p.a.cin_pad // 16) > WSTREAM_MAX_STEPS:
-            return False
-        if a.act == ACT["gauss"] and p.pk.cout % 16:
-            return False
-    return True
 
 
 def _candidates(M, cout, nst, nks=None, plain=True, spatial=False, smallk=False, wstream=False):
@@ -630,179 +538,104 @@ def prepare(pk, srcs, out=None, out_coff=0, act="none", act_param=0.0, res0=None
     return pr
 
 
-def _spatial_ok(preps):
-    a = preps[0].a
-    return (a.dtype == _lib.BF16 and a.mode == CONV and a.ksize == 3 and a.stride == 1 and
-            a.in_h % 16 == 0 and a.in_w % 16 == 0 and a.act != ACT["gauss"] and
-            all(p.a.nsrc == 1 and p.a.cin_pad == 32 and p.a.src[0].channels == 32 and
-                p.a.cout <= 32 for p in preps))
-
-
-# C++ template arguments (BM, BN, WGM, WGN, NBUF) of the streaming/persistent tiles, so the
-# profiler's kernel names are exactly rocprofv3's (csrc/conv.hip launch_conv).
-_TILE_SIG = {0: "128, 128, 2, 2, 2", 1: "128, 64, 4, 1, 3", 2: "64, 64, 2, 2, 3",
-             3: "128, 32, 4, 1, 3", 4: "64, 32, 2, 2, 3", 5: "128, 16, 4, 1, 3",
-             6: "64, 16, 4, 1, 3", 20: "128, 128, 2, 2, 2, 2", 21: "128, 64, 4, 1, 2, 2",
-             22: "64, 64, 2, 2, 2, 2", 23: "128, 32, 4, 1, 2, 2", 24: "64, 32, 2, 2, 3, 2",
-             25: "128, 16, 4, 1, 2, 2", 26: "64, 16, 4, 1, 3, 2"}
-_SMALLK_NKS = {1: 1, 2: 2, 3: 3, 4: 4, 5: 5, 6: 6, 7: 8, 8: 8, 9: 12, 10: 12, 11: 12, 12: 12}
-
-
-_PW2_ON = os.environ.get("RGBAC_PW2", "1") != "0"
-_PW2_ALL = os.environ.get("RGBAC_PW2_ALL", "1") != "0"
-
-
-def _pw2_admits(preps):
-    """Host mirror of csrc/conv.hip pw2_ok (which pointwise kernel a TILE_PW launch runs)."""
-    a0 = preps[0].a
-    if not _PW2_ON or a0.act in (ACT["tanh_half"], ACT["gauss"]) or a0.mode != CONV:
-        return False
-    if not _PW2_ALL and -(-preps[0].mgrid // 16) * len(preps) > 8 * 256:
-        return False
-    for p in preps:
-        a = p.a
-        if (a.zout and a.zout_ldc % 4) or a.cout % 8 or a.out_coff % 8 or a.out_ldc % 8 or \
-                a.cout > 192 or (a.res0 and a.res0_ldc % 4) or (a.res1 and a.res1_ldc % 4) or \
-                (a.res2 and a.res2_ldc % 4):
-            return False
-    return True
-
-
-_PW3_ON = os.environ.get("RGBAC_PW3", "1") != "0"
-
-
-def _pw3_admits(preps):
-    """Host mirror of csrc/pw3.hip pw3_ok: the two-deep GDN / IGDN forward kernel."""
-    a0 = preps[0].a
-    gate = a0.act == ACT["gate"] and preps[0].mgrid >= 8192 * 16
-    if not _PW3_ON or (a0.act not in (ACT["gdn"], ACT["igdn"]) and not gate) or \
-            bool(a0.square_input) == gate or a0.mode != CONV:
-        return False
-    if not 128 < max(p.a.cin_pad for p in preps) <= 192:
-        return False
-    for p in preps:
-        a = p.a
-        if a.res0 or a.zout or a.cout != 192 or a.out_coff % 8 or a.out_ldc % 8 or \
-                a.src[0].ldc % 8 or a.k_pad < a.cin_pad:
-            return False
-        if gate:
-            if not a.res1 or not a.res2 or a.res1_ldc % 4 or a.res2_ldc % 4:
-                return False
-        elif a.res1 != a.src[0].ptr or a.res1_ldc != a.src[0].ldc or a.res2:
-            return False
-    return True
+def _describe(t, ks, preps):
+    """(status, kernel name) of a (tile, ksplit) launch of these grouped convs, from the
+    library's own validation and kernel decision (rgbac_conv2d_grouped_describe: nothing is
+    launched, no pointer dereferenced, no GPU needed)."""
+    n = len(preps)
+    arr = (_lib.ConvArgs * n)()
+    for i, pr in enumerate(preps):
+        arr[i] = pr.a
+        arr[i].tile, arr[i].ksplit = t, ks
+    name = ctypes.create_string_buffer(96)
+    rc = _lib.load().rgbac_conv2d_grouped_describe(ctypes.addressof(arr), n, name, len(name))
+    return rc, name.value.decode()
 
 
 def kernel_name(tile, preps):
     """rocprofv3-style name (namespace and argument list stripped) of a conv launch."""
-    dt = "float" if preps[0].a.dtype == 0 else "bf16_t"
-    if tile == TILE_SPATIAL:
-        return f"conv3x3_c32_kernel<{dt}>"
-    if tile in FPATCH_KS:
-        return "conv_fpatch_kernel<%d, %d, %d, 4, %d, 3>" % (FPATCH_SIG[tile] + (FPATCH_KS[tile],
-                                                                           fpatch_cpt_ks(preps, tile)))
-    if tile in FPATCH_SIG:
-        c = fpatch_cpt(preps) if FPATCH_SIG[tile][0] == 4 else 0
-        return "conv_fpatch_kernel<%d, %d, 4, 4%s>" % (FPATCH_SIG[tile] + (f", {c}" if c else "",))
-    if tile in PATCH_SIG:
-        dact = "true" if preps[0].a.act in (ACT["dgelu"], ACT["dlrelu"]) else "false"
-        return "conv_patch_kernel<%d, %d, %d, %d, %d, %s>" % (PATCH_SIG[tile] + (dact,))
-    if tile == TILE_WSTREAM:
-        # the library's wave count choice (csrc/conv.hip launch_wstream)
-        nks = max((p.a.ksize * p.a.ksize * p.a.cin_pad + 15) // 16 for p in preps)
-        env = os.environ.get("RGBAC_WSTREAM_WAVES", "")
-        nw = int(env) if env in ("4", "8") else (8 if nks >= 64 else 4)
-        return f"conv_wstream_kernel<8, {nw}>"
-    if tile == TILE_NPATCH:
-        return f"conv_npatch_kernel<{2 if max(p.pk.cout for p in preps) > 16 else 1}>"
-    if tile == TILE_PW:
-        cin = max(p.a.cin_pad for p in preps)
-        nks = 2 if cin <= 64 else (4 if cin <= 128 else 6)
-        # csrc/conv.hip launch_pw: conv_pw2_kernel where pw2_ok admits the launch, else
-        # conv_pw_kernel (32-deep k-steps held in LDS: 2 / 4 / 6)
-        if _pw3_admits(preps):
-            return f"conv_pw3_kernel<6, {preps[0].a.act}>"
-        if _pw2_admits(preps):
-            return f"conv_pw2_kernel<{nks}>"
-        dact = "true" if preps[0].a.act in (ACT["dgelu"], ACT["dlrelu"]) else "false"
-        return f"conv_pw_kernel<{nks}, {dact}>"
-    if tile == TILE_SMALLK:
-        cout = max(p.pk.cout for p in preps)
-        nt = 1 if cout <= 32 else (2 if cout <= 64 else 3)
-        nks = -(-max(p.a.cin_pad for p in preps) // 16)
-        return f"conv_smallk_kernel<{nt}, {_SMALLK_NKS.get(nks, 16)}>"
-    if FIRST_DIRECT <= tile < FIRST_DEEP:
-        return f"conv_direct_kernel<{dt},{TILES[tile][1] // 16}>"
-    if FIRST_WRES <= tile < FIRST_DIRECT:
-        bm, bn = TILES[tile]
-        return f"conv_wres_kernel<{dt},{bm}x{bn}>"
-    if tile >= FIRST_PERS:
-        return f"conv_pers_kernel<{dt}, {_TILE_SIG[tile - FIRST_PERS]}>"
-    # tiles 0..6 instantiate conv_kernel's KSM = 1 default (rocprofv3 prints it)
-    return f"conv_kernel<{dt}, {_TILE_SIG[tile]}{', 1' if tile < FIRST_WRES else ''}>"
+    rc, name = _describe(tile, 1, preps)
+    if rc != 0:
+        raise RuntimeError(f"tile {tile} does not take these convs: "
+                           f"{_lib.load().rgbac_last_error().decode(errors='replace')}")
+    return name
 
 
 # RGBAC_NPATCH_SUBPEL=0: keep subpel convs off the narrow patch tile (A/B against older builds)
 NPATCH_SUBPEL = os.environ.get("RGBAC_NPATCH_SUBPEL", "1") != "0"
 
 
+def _choice_valid(t, preps, ks=1):
+    """Whether tile ``t`` with split ``ks`` accepts these (grouped) convs: the library says
+    (its launcher's own checks).  Added here only what it cannot know -- whether the packs
+    have the fragment-major copy the tile reads -- and the RGBAC_PATCH / RGBAC_NPATCH_SUBPEL
+    policy switches and _patch_split_ok (no phase split of a folded activation backward)."""
+    if t in FRAG_TILES and not all(_has_frag(p.pk) for p in preps):
+        return False
+    if (not PATCH and (t in PATCH_SIG or t in FPATCH_SIG)) or \
+            (ks > 1 and t in PATCH_SIG and not _patch_split_ok(preps)) or \
+            (not NPATCH_SUBPEL and t == TILE_NPATCH and preps[0].a.mode == SUBPEL2):
+        return False
+    # policy: subpel convs are offered only the first two K-split fragment-patch tiles (the
+    # ones with the 8..10 k-step variants their 256..320-channel inputs need); the library
+    # also takes a 96 / 128 / 224-channel subpel conv on the others, which nothing has timed
+    if preps[0].a.mode == SUBPEL2 and t in _KS_NO_SUBPEL:
+        return False
+    return _describe(t, ks, preps)[0] == 0
+
+
 def _npatch_ok(preps):
-    a = preps[0].a
-    # subpel convs (the decoder's 3-channel ConvTranspose as conv3x3 + PixelShuffle) take the
-    # plain epilogue: bias, optional GELU, shuffled store -- no residual operands
-    subpel_ok = (NPATCH_SUBPEL and a.mode == SUBPEL2 and a.act in (ACT["none"], ACT["gelu"]) and
-                 all(not (p.a.res0 or p.a.res1 or p.a.res2) for p in preps))
-    if not (a.dtype == _lib.BF16 and (a.mode == CONV or subpel_ok) and a.ksize == 3 and
-            a.stride == 1 and a.in_w % 16 == 0 and a.in_h % 4 == 0 and
-            a.batch * a.in_h * a.in_w < (1 << 24)):
-        return False
-    if not all(_has_frag(p.pk) for p in preps) or a.act in (ACT["dgelu"], ACT["dlrelu"]):
-        return False
-    for p in preps:
-        if p.pk.cout > 32 or 6 * 18 * (round_up(p.pk.cin_pad, 32) // 8 + 2) * 16 > 128 * 1024:
-            return False
-        if a.act == ACT["gauss"] and p.pk.cout not in (16, 32):
-            return False
-    return True
+    return _choice_valid(TILE_NPATCH, preps)
 
 
-def _pw_ok(preps):
-    a = preps[0].a
-    return (a.dtype == _lib.BF16 and a.mode == CONV and a.act != ACT["gauss"] and
-            a.ksize == 1 and a.stride == 1 and
-            all(p.a.nsrc == 1 and p.a.cin_pad <= 192 and p.pk.cout <= 192 for p in preps))
-
-
-def _smallk_ok(preps):
-    a = preps[0].a
-    return (a.dtype == _lib.BF16 and a.mode == CONV and a.act != ACT["gauss"] and
-            a.ksize == 1 and a.stride == 1 and
-            all(p.a.nsrc == 1 and p.a.cin_pad <= SMALLK_MAX for p in preps))
+def _patch_tiles(preps):
+    """Patch-resident and fragment-streamed patch tiles that apply to these (grouped) convs."""
+    return [t for t in (*PATCH_SIG, *FPATCH_SIG) if _choice_valid(t, preps)]
 
 
 def _gauss_ok(t, cout):
     return TILES[t][1] >= cout
 
 
-def _choice_valid(t, preps):
-    """Whether tile ``t`` accepts these (grouped, non-GAUSS) convs: the special tiles have
-    the preconditions their launchers check (csrc/conv.hip RGBAC_REQUIRE); the streaming /
-    persistent / weight-resident tiles take any conv."""
-    if t == TILE_PW:
-        return _pw_ok(preps)
-    if t == TILE_NPATCH:
-        return _npatch_ok(preps)
-    if t == TILE_WSTREAM:
-        return _wstream_ok(preps)
-    if t == TILE_SMALLK:
-        return _smallk_ok(preps)
-    if t == TILE_SPATIAL:
-        return _spatial_ok(preps)
-    if t >= FIRST_PATCH:
-        return t in _patch_tiles(preps)
-    if FIRST_DIRECT <= t < FIRST_DEEP:
-        return preps[0].pk.mode == CONV
-    return True
+def candidates(preps, phase_split=True):
+    """(tile, ksplit) pairs worth timing for these grouped convs, every one of them valid;
+    ``phase_split``: also the conv_patch_kernel tiles with the phase split where it applies."""
+    p0 = preps[0]
+    cout = max(pr.pk.cout for pr in preps)
+
+    def ok(t):
+        return _choice_valid(t, preps)
+    if p0.a.act == ACT["gauss"]:
+        cands = [(t, 1) for t in GAUSS_TILES if _gauss_ok(t, cout)]
+        cands += [(t, 1) for t in (TILE_WSTREAM, TILE_NPATCH) if ok(t)]
+    else:
+        cands = _candidates(p0.mgrid * p0.nphase * len(preps), cout, max(pr.nst for pr in preps),
+                            max(pr.nks for pr in preps), p0.pk.mode == CONV, ok(TILE_SPATIAL),
+                            ok(TILE_SMALLK), ok(TILE_WSTREAM))
+        patch = _patch_tiles(preps)
+        cands += [(t, 1) for t in patch]
+        if phase_split and _patch_split_ok(preps):
+            cands += [(t, 4) for t in patch if t in PATCH_SIG]
+        cands += [(t, 1) for t in (TILE_PW, TILE_NPATCH) if ok(t)]
+    return [c for c in cands if _choice_valid(c[0], preps, c[1])]
+
+
+def resolve_choice(choice, preps):
+    """What launch() makes of a cached / forced (tile, ksplit): itself where the tile takes
+    THESE convs, else the shape rule.  The cache key (dtype / mode / ksize / stride / shape /
+    cin_pad / cout) does not hold the source count, the residual operands, the activation or
+    the pack type, so the same key can come from a conv the special tiles accept (e.g.
+    TILE_PW tuned on a one-source conv, handed a two-source one), or a fragment-streamed tile
+    tuned on a pack with a fragment-major copy handed one without it, or an input-gradient
+    conv with the folded activation backward (not in those tiles)."""
+    if _choice_valid(choice[0], preps, choice[1]):
+        return tuple(choice)
+    p0 = preps[0]
+    if p0.a.act == ACT["gauss"]:
+        return (min((t for t in GAUSS_TILES if _gauss_ok(t, p0.pk.cout)),
+                    key=lambda t: TILES[t][1]), 1)
+    return _heuristic(p0.mgrid * p0.nphase * len(preps), max(pr.pk.cout for pr in preps),
+                      max(pr.nst for pr in preps))
 
 
 # Split-K tickets for the in-launch reduction (rgbac_conv_args.tile_counters): one zeroed
@@ -883,22 +716,8 @@ def launch(preps, force=None):
         mtot = p0.mgrid * p0.nphase * n
         cout = max(pr.pk.cout for pr in preps)
         nst = max(pr.nst for pr in preps)
-        if gauss:
-            cands = [(t, 1) for t in GAUSS_TILES if _gauss_ok(t, cout)]
-            if _wstream_ok(preps):
-                cands.append((TILE_WSTREAM, 1))
-            if _npatch_ok(preps):
-                cands.append((TILE_NPATCH, 1))
-        else:
-            cands = _candidates(mtot, cout, nst, max(pr.nks for pr in preps),
-                                p0.pk.mode == CONV, _spatial_ok(preps), _smallk_ok(preps),
-                                _wstream_ok(preps))
-            cands += _patch_cands(preps)
-            if _pw_ok(preps):
-                cands.append((TILE_PW, 1))
-            if _npatch_ok(preps):
-                cands.append((TILE_NPATCH, 1))
         if TUNE and not fixed and not torch.cuda.is_current_stream_capturing():
+            cands = candidates(preps)
             # each timed run starts with the L2s flushed (a 64 MB write evicts all 8 XCDs'
             # 4 MB): in the forward graph every layer's weights and inputs arrive cold, and a
             # candidate that re-streams its weights per wave from L2 looks 2x faster hot
@@ -950,29 +769,12 @@ def launch(preps, force=None):
                 torch.cuda.synchronize(dev)
                 del scratch
         elif gauss:
-            choice = min(cands, key=lambda c: TILES[c[0]][1])
+            choice = min(candidates(preps), key=lambda c: TILES[c[0]][1])
         else:
             choice = _heuristic(mtot, cout, nst)
         if not fixed:
             _tune_cache[key] = choice
-    if not gauss and (not _choice_valid(choice[0], preps) or (
-            choice[1] > 1 and choice[0] in PATCH_SIG and
-            (choice[1] != 4 or not _patch_split_ok(preps)))):
-        # a cached / forced tile the C side would refuse for THESE convs: the cache key
-        # (dtype / mode / ksize / stride / shape / cin_pad / cout) does not hold the source
-        # count, the residual operands, the activation or the pack type, so the same key
-        # can come from a conv the special tiles accept (e.g. TILE_PW tuned on a
-        # one-source conv, handed a two-source one), or a fragment-streamed tile tuned on a
-        # pack with a fragment-major copy handed one without it, or an input-gradient conv
-        # with the folded activation backward (not in those tiles) -- take the shape rule
-        choice = _heuristic(p0.mgrid * p0.nphase * n, max(pr.pk.cout for pr in preps),
-                            max(pr.nst for pr in preps))
-    if gauss and not (choice[0] == TILE_WSTREAM and _wstream_ok(preps)) and \
-            not (choice[0] == TILE_NPATCH and _npatch_ok(preps)) and (
-            choice[0] not in GAUSS_TILES or
-            not _gauss_ok(choice[0], max(pr.pk.cout for pr in preps))):
-        choice = (min((t for t in GAUSS_TILES if _gauss_ok(t, p0.pk.cout)),
-                      key=lambda t: TILES[t][1]), 1)
+    choice = resolve_choice(choice, preps)
     set_choice(*choice)
     LAST_CHOICE[0] = tuple(choice)
     if PROFILER is None:

@@ -148,6 +148,20 @@ int rgbac_conv_num_tiles(void);
  * 0 for the plain [nphase][cout_pad][k_pad] pack, -1 if out of range. */
 int rgbac_conv_tile_weight_layout(int tile);
 
+/* Where a tile is described: ONE table in csrc/conv.hip (kTiles: kind, bm x bn pixels x
+ * channels, the kernel's template arguments) that the launcher validates against, picks the
+ * kernel instantiation from and instantiates the kernels with.  rgbac_conv_tile_info reads
+ * that table for the host runtime; no other copy of it exists. */
+enum rgbac_tile_kind {
+  RGBAC_TILE_STREAM = 0, RGBAC_TILE_DEEP = 1, RGBAC_TILE_PERS = 2, RGBAC_TILE_WRES = 3,
+  RGBAC_TILE_DIRECT = 4, RGBAC_TILE_SPATIAL = 5, RGBAC_TILE_SMALLK = 6, RGBAC_TILE_WSTREAM = 7,
+  RGBAC_TILE_PATCH = 8, RGBAC_TILE_FPATCH = 9, RGBAC_TILE_FPATCH_KS = 10, RGBAC_TILE_PW = 11,
+  RGBAC_TILE_NPATCH = 12,
+};
+/* bm, bn (pixels x channels) and rgbac_tile_kind of `tile`; any out pointer may be NULL.
+ * RGBAC_E_ARG if `tile` is out of range. */
+int rgbac_conv_tile_info(int tile, int* bm, int* bn, int* kind);
+
 /* ngroups (1..rgbac_conv_max_groups()) independent convs in one launch.  All
  * groups share dtype, mode, batch, input/output size, ksize, stride, tile,
  * ksplit, act/act_param and square_input; weights, sources (cin may differ),
@@ -162,6 +176,20 @@ int rgbac_conv_max_groups(void);
  * launch profiler): part 1 = the main conv kernel only, part 2 = the split-K reduce +
  * epilogue kernels only (a no-op when ksplit == 1), part 0 = both (== grouped). */
 int rgbac_conv2d_grouped_part(const rgbac_conv_args* args, int ngroups, int part, void* stream);
+
+/* The validation and kernel decision of rgbac_conv2d_grouped without the launch: the two
+ * share one code path, so what this accepts and names is what a launch accepts and runs
+ * (which tile kinds take these convs, and the inner choices: pw3 / pw2 / pw and its NKS, the
+ * wstream wave count, smallk NT / NKS, npatch TN, fpatch CPT, patch DACT).  RGBAC_OK: the
+ * kernel's name as rocprofv3 prints it (namespace and argument list stripped, e.g.
+ * "conv_kernel<bf16_t, 128, 64, 4, 1, 3, 1>") is written to kernel[cap] (NUL-terminated,
+ * truncated to cap; kernel may be NULL).  On refusal: the launch's status code and
+ * rgbac_last_error text.  Makes no HIP call and dereferences no pointer in `args` (null-ness,
+ * alignment and equality of pointers are looked at), so it runs without a GPU.  Exempt from
+ * the checks: the buffers that exist only once a (tile, ksplit) choice is set -- `workspace`
+ * (split-K) and `tile_counters` may be NULL here. */
+int rgbac_conv2d_grouped_describe(const rgbac_conv_args* args, int ngroups, char* kernel,
+                                  int cap);
 
 /* Attention core of masked shifted-window MSA on a precomputed qkv tensor
  * (qkv = Linear(C,3C) applied per pixel by rgbac_conv2d).  For every window

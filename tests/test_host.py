@@ -34,6 +34,15 @@ def test_library_exports_every_header_symbol():
     assert lib.rgbac_abi_version() == 2
     from rgbac import runtime as rt
     assert lib.rgbac_conv_num_tiles() == len(rt.TILES)
+    kinds = set()
+    for t, (bm, bn) in enumerate(rt.TILES):
+        v = [ctypes.c_int(-1) for _ in range(3)]
+        assert lib.rgbac_conv_tile_info(t, *(ctypes.byref(x) for x in v)) == 0
+        assert (v[0].value, v[1].value) == (bm, bn), t
+        assert 0 <= v[2].value < len(_lib.TILE_KINDS), t
+        kinds.add(v[2].value)
+    assert len(kinds) == len(_lib.TILE_KINDS)                  # every kind has a tile
+    assert lib.rgbac_conv_tile_info(len(rt.TILES), None, None, None) != 0
     assert lib.rgbac_conv_max_groups() == 10
 
 
@@ -165,10 +174,11 @@ def test_tile_candidates():
 
 
 def test_pw3_admission_mirror():
-    """rgbac.runtime._pw3_admits (the host mirror of csrc/pw3.hip pw3_ok, which names the
-    pointwise kernel in the bench tables): GDN / IGDN with x as the epilogue operand and 192
-    channels; the gate only with both operands and from 8,192 tiles on; never a pre-activation
-    store, a res0 operand or a 96-channel input."""
+    """Which pointwise kernel the library runs for a TILE_PW launch (csrc/pw3.hip pw3_ok, asked
+    through rgbac_conv2d_grouped_describe; the name labels the bench tables): conv_pw3_kernel
+    for GDN / IGDN with x as the epilogue operand and 192 channels; for the gate only with both
+    operands and from 8,192 tiles on; never with a pre-activation store, a res0 operand or a
+    96-channel input."""
     import types
     from rgbac import _lib
     from rgbac import runtime as rt
@@ -176,27 +186,35 @@ def test_pw3_admission_mirror():
     def prep(act, cin=192, cout=192, square=True, res1="x", res2=False, res0=False, zout=False,
              mgrid=8 * 64 * 64):
         a = _lib.ConvArgs()
+        side = int((mgrid // 8) ** 0.5)
+        a.dtype, a.batch, a.in_h, a.in_w, a.out_h, a.out_w = _lib.BF16, 8, side, side, side, side
+        a.ksize, a.stride, a.nsrc = 1, 1, 1
         a.mode, a.act, a.square_input = rt.CONV, rt.ACT[act], 1 if square else 0
-        a.cin_pad, a.k_pad, a.cout, a.out_ldc, a.out_coff = cin, cin, cout, cout, 0
-        a.src[0].ptr, a.src[0].ldc = 4096, cin
+        a.cin_pad, a.k_pad, a.cout, a.out_ldc, a.out_coff = cin, rt.round_up(cin, 64), cout, cout, 0
+        a.cout_pad, a.weight, a.out = 256, 24576, 28672
+        a.src[0].ptr, a.src[0].ldc, a.src[0].channels = 4096, cin, cin
         a.res1 = 4096 if res1 == "x" else (8192 if res1 else None)
         a.res1_ldc = cin if res1 == "x" else cout
         a.res2, a.res2_ldc = (12288 if res2 else None), cout
         a.res0, a.zout = (16384 if res0 else None), (20480 if zout else None)
+        a.res0_ldc = a.zout_ldc = cout
         return types.SimpleNamespace(a=a, mgrid=mgrid)
 
-    assert rt._pw3_admits([prep("gdn")]) and rt._pw3_admits([prep("igdn")])
-    assert rt._pw3_admits([prep("gdn"), prep("gdn")])
-    assert not rt._pw3_admits([prep("gdn", zout=True)])
-    assert not rt._pw3_admits([prep("gdn", res0=True)])
-    assert not rt._pw3_admits([prep("gdn", cin=96)])
-    assert not rt._pw3_admits([prep("gdn", cout=96)])
-    assert not rt._pw3_admits([prep("gdn", res1="a")])          # x must be the epilogue operand
+    def pw3(preps):
+        return rt.kernel_name(rt.TILE_PW, preps).startswith("conv_pw3_kernel")
+
+    assert pw3([prep("gdn")]) and pw3([prep("igdn")])
+    assert pw3([prep("gdn"), prep("gdn")])
+    assert not pw3([prep("gdn", zout=True)])
+    assert not pw3([prep("gdn", res0=True)])
+    assert not pw3([prep("gdn", cin=96)])
+    assert not pw3([prep("gdn", cout=96)])
+    assert not pw3([prep("gdn", res1="a")])          # x must be the epilogue operand
     gate = dict(square=False, res1="a", res2=True)
-    assert not rt._pw3_admits([prep("gate", **gate)])           # 2,048 tiles: stays on pw2
-    assert rt._pw3_admits([prep("gate", mgrid=8 * 128 * 128, **gate)])
-    assert not rt._pw3_admits([prep("gate", mgrid=8 * 128 * 128, square=False, res1="a")])
-    assert not rt._pw3_admits([prep("gelu", square=False, res1=None)])
+    assert not pw3([prep("gate", **gate)])           # 2,048 tiles: stays on pw2
+    assert pw3([prep("gate", mgrid=8 * 128 * 128, **gate)])
+    assert not pw3([prep("gate", mgrid=8 * 128 * 128, square=False, res1="a")])
+    assert not pw3([prep("gelu", square=False, res1=None)])
 
 
 def test_state_dict_layout_matches_reference_names():

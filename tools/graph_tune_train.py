@@ -60,18 +60,7 @@ def main():
     flush = torch.zeros(16 << 20, device=dev)
 
     def cands_of(preps):
-        p0 = preps[0]
-        n = len(preps)
-        c = rt._candidates(p0.mgrid * p0.nphase * n, max(p.pk.cout for p in preps),
-                           max(p.nst for p in preps), max(p.nks for p in preps),
-                           p0.pk.mode == rt.CONV, rt._spatial_ok(preps), rt._smallk_ok(preps),
-                           rt._wstream_ok(preps))
-        c += [(t, 1) for t in rt._patch_tiles(preps)]
-        if rt._pw_ok(preps):
-            c.append((rt.TILE_PW, 1))
-        if rt._npatch_ok(preps):
-            c.append((rt.TILE_NPATCH, 1))
-        return c
+        return rt.candidates(preps, phase_split=False)
 
     # ---- cold timing of each shape's candidates (the tuner's method) INSIDE one eager forward,
     # at the launch itself while its operands are live: a recorded launch replayed after the

@@ -58,9 +58,9 @@ def main():
             preps.append(prep_subpel(m, [x.src()]) if kind == "subpel"
                          else prep_conv(m, [x.src()], act="none" if kind in ("s2", "convt") else "gelu"))
         flops = sum(p.flops for p in preps)
-        cands = rt._candidates(preps[0].mgrid * preps[0].nphase * G, cout, preps[0].nst,
-                               preps[0].nks, preps[0].pk.mode == rt.CONV, False, False, False)
-        cands += rt._patch_cands(preps)
+        # the im2col and patch tiles only (none of the 1x1 / narrow-output special tiles)
+        cands = [c for c in rt.candidates(preps) if c[0] not in (
+            rt.TILE_SPATIAL, rt.TILE_SMALLK, rt.TILE_WSTREAM, rt.TILE_PW, rt.TILE_NPATCH)]
         if args.tile is not None:
             cands = [(args.tile, 1)]
         res = []

@@ -79,15 +79,7 @@ def main():
                 preps.append(prep_subpel(m, srcs))
             else:
                 preps.append(prep_conv(m, srcs, act="gelu"))
-        p0 = preps[0]
-        cands = rt._candidates(p0.mgrid * p0.nphase * G, cout, max(p.nst for p in preps),
-                               max(p.nks for p in preps), p0.pk.mode == rt.CONV,
-                               rt._spatial_ok(preps), rt._smallk_ok(preps), rt._wstream_ok(preps))
-        cands += [(t, 1) for t in rt._patch_tiles(preps)]
-        if rt._pw_ok(preps):
-            cands.append((rt.TILE_PW, 1))
-        if rt._npatch_ok(preps):
-            cands.append((rt.TILE_NPATCH, 1))
+        cands = rt.candidates(preps, phase_split=False)
         flops = sum(p.flops for p in preps)
         res = []
         with torch.no_grad():
