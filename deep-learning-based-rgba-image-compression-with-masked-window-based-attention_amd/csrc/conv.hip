@@ -459,6 +459,28 @@ __global__ void __launch_bounds__(256) conv_pers_kernel(const ConvArgsDev args) 
   const int s_end = (int)((long long)nst * (split + 1) / s.ksplit);
   const int ns = s_end - s_beg;
   const int nq = mytiles * ns;
+  if (ns == 0) {
+    // an empty K range (more splits than K stages): nothing to stream, but the split-K
+    // epilogue sums every slab, so this split's part of its tiles is written as zeros
+    const int wm_ = wave % WGM, wn_ = wave / WGM, fr_ = lane & 15, fq_ = lane >> 4;
+    for (int ti = 0; ti < mytiles; ++ti) {
+      const int f = (int)blockIdx.x + ti * G;
+      const int n0 = (f % Nb) * BN, m0 = (f / Nb) * BM;
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        const int m = m0 + wm_ * TM * 16 + i * 16 + fr_;
+        if (m >= s.M) continue;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          const int n = n0 + wn_ * TN * 16 + j * 16 + fq_ * 4;
+          if (n >= g.cout) continue;
+          float* w = g.ws + (((size_t)split * s.nphase + phase) * s.M + m) * g.cout16 + n;
+          *reinterpret_cast<float4*>(w) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+      }
+    }
+    return;
+  }
 
   const int in_h = s.in_h, in_w = s.in_w, cin_pad = g.cin_pad, Mtot = s.M;
   const int Wm = s.Wm, Hm = s.Hm, sy = s.sy;
@@ -902,7 +924,10 @@ __global__ void __launch_bounds__(256) conv_direct_kernel(const ConvArgsDev args
       }
     }
     if (m < s.M) {
-      constexpr int CH = NT < 4 ? NT : 4;          // epilogue in chunks of <= 4 tiles
+      // epilogue in chunks of <= 4 tiles that divide NT (NT = 6: 3 + 3; a chunk of 4 would
+      // run its second turn over acc[6], acc[7] and store them as channels n0 + 96 ..)
+      constexpr int CH = NT % 4 == 0 ? 4 : NT % 3 == 0 ? 3 : NT % 2 == 0 ? 2 : 1;
+      static_assert(NT % CH == 0, "the epilogue chunks cover acc[NT] exactly");
 #pragma unroll
       for (int j0 = 0; j0 < NT; j0 += CH) {
         int nn[CH];
