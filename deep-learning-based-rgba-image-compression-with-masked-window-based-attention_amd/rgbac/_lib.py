@@ -87,6 +87,14 @@ class RansDecoderState(ctypes.Structure):
                 ("pos", ctypes.c_int64)]
 
 
+class ImageDesc(ctypes.Structure):
+    """rgbac_image_desc"""
+    _fields_ = [("ptr", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
+                ("row_stride_bytes", ctypes.c_int64)]
+
+
+PAD_MODES = dict(transparent=0, replicate=1)   # enum rgbac_pad_mode
+
 _VP, _I32, _I64, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 _D = ctypes.c_double
 # name -> argtypes (restype int unless noted); must match include/rgbac.h
@@ -176,6 +184,13 @@ SIGNATURES = {
     # RGBA eval pipeline (alpha recon -> RGB codec)
     "rgbac_alpha_recon": [_I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP],
     "rgbac_rgba_finish": [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    # images of any size (pad / crop / region error around the codecs)
+    "rgbac_rgba_pack": [_I32, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP],
+    "rgbac_pad_nchw": [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP],
+    "rgbac_rgba_unpack": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP],
+    "rgbac_region_error_blocks": [_I32, _I32],
+    "rgbac_region_error": [_I32, _I32, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                           _VP],
     # MS-SSIM metric
     "rgbac_ssim_level": [_I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _F, _F, _VP, _VP, _VP, _VP],
     "rgbac_avgpool2": [_I32, _I32, _I32, _VP, _VP, _VP],

@@ -659,6 +659,51 @@ int rgbac_rgba_finish(int64_t n, const float* x_hat, float* x_out, const float* 
                       const float* bpp_mask, const int32_t* not_all_ones, const float* mse,
                       float* bpp_total, float* psnr, void* stream);
 
+/* Images of any size (csrc/anysize.hip): the pad / crop / region-error layer around the two
+ * codecs, which only take heights and widths that are multiples of 64.  A batch of images
+ * (h_b, w_b) shares one canvas hp x wp = round_up(max h_b, 64) x round_up(max w_b, 64), each
+ * image at the top-left.  descs: DEVICE array of `batch` rgbac_image_desc; ptr is 4-byte
+ * aligned, row_stride_bytes a multiple of 4 and >= 4 w (rows may start at any pixel of a larger
+ * buffer).  Canvas tensors are fp32 NCHW, contiguous, 16-byte aligned.  Pad modes: outside an
+ * image's rectangle the canvas holds 0 (RGBAC_PAD_TRANSPARENT) or the image's value at
+ * (min(r, h_b-1), min(c, w_b-1)) (RGBAC_PAD_REPLICATE).
+ * rgbac_rgba_pack: uint8 RGBA sources (h_b, w_b, 4) -> alpha (B,1,hp,wp) = A/255, rgb
+ *   (B,3,hp,wp) = {R,G,B}/255 (IEEE division: torch's u8.float().div(255) bit for bit) and
+ *   masked (B,3,hp,wp) = alpha > 0 ? rgb : alpha (my_datasets/MYdataset.py:113), then the pad
+ *   mode; any output may be NULL (not all).  One launch for the batch.
+ * rgbac_pad_nchw: x (B,C,h,w) -> out (B,C,hp,wp), h <= hp, w <= wp, either mode; out must not
+ *   alias x.
+ * rgbac_rgba_unpack: x_hat (B,3,hp,wp) and alpha (B,1,hp,wp; NULL = 255) -> uint8 RGBA written
+ *   to each descriptor's (h_b, w_b, 4) destination, cropped to it (bytes outside stay
+ *   untouched): u8 = (uint8) clamp(x*255 + 0.5, 0, 255), the multiply and the add each rounded
+ *   in fp32 (torchvision save_image after the clamp of trainRGB.py:290,295-297; no FMA).
+ *   zero_transparent != 0 writes R = G = B = 0 where the alpha byte is 0.
+ * rgbac_region_error: reconstruct_error (models/AutoEncoderRGB_Journal.py:36-64) restricted to
+ *   each image's rectangle (descs[b].h / .w; ptr unused).  x, y (B,C,hp,wp), mask (B,1,hp,wp) or
+ *   NULL; per image sse = sum over c, r < h_b, col < w_b, mask > 0 of (double(x) - double(y))^2,
+ *   n = C * #{mask > 0 in the rectangle} (C h_b w_b without a mask), mse = float(sse /
+ *   max(n, 1)), psnr = float(10 log10(1 / mse)), 100 when sse == 0 (trainRGB.py:202-206).
+ *   Values outside the rectangle are never read into a result.  Fixed summation order, no
+ *   atomics: bit-reproducible.  scratch: batch * rgbac_region_error_blocks(hp, wp) * 2 doubles
+ *   (no initial contents needed); any of sse / n / mse / psnr may be NULL. */
+enum rgbac_pad_mode { RGBAC_PAD_TRANSPARENT = 0, RGBAC_PAD_REPLICATE = 1 };
+typedef struct rgbac_image_desc {
+  void* ptr;                 /* first pixel of the image (uint8 RGBA, interleaved) */
+  int32_t h, w;              /* real size */
+  int64_t row_stride_bytes;  /* bytes from one row's start to the next */
+} rgbac_image_desc;
+int rgbac_rgba_pack(int batch, const rgbac_image_desc* descs, int hp, int wp, int mode,
+                    float* alpha, float* rgb, float* masked, void* stream);
+int rgbac_pad_nchw(int batch, int channels, int h, int w, int hp, int wp, int mode,
+                   const float* x, float* out, void* stream);
+int rgbac_rgba_unpack(int batch, const rgbac_image_desc* descs, int hp, int wp,
+                      const float* x_hat, const float* alpha, int zero_transparent,
+                      void* stream);
+int rgbac_region_error_blocks(int hp, int wp);
+int rgbac_region_error(int batch, int channels, const rgbac_image_desc* descs, int hp, int wp,
+                       const float* x, const float* y, const float* mask, double* scratch,
+                       double* sse, int64_t* n, float* mse, float* psnr, void* stream);
+
 /* MS-SSIM / SSIM metric (csrc/msssim.hip), replaces metrics/ms_ssim_torch.py:5-194.
  * fp32 NCHW planes.  rgbac_ssim_level: one scale of _ssim (:36-83) with the VALID 1-D gaussian
  *   win[win_size] (W pass then H pass, :21-33), C1 = (K1*range)^2, C2 = (K2*range)^2;
