@@ -8,6 +8,9 @@
 //   * rgba_pack_kernel:    ragged uint8 RGBA (h_b, w_b, 4) -> padded fp32 NCHW alpha / rgb /
 //                          masked = where(alpha > 0, rgb, alpha) (MYdataset.py:113), /255 by
 //                          IEEE division (ToTensor);
+//   * rgba_opaque_*:       per image, whether every alpha byte of its rectangle is 255 (what
+//                          decides replicate padding and "no alpha stream" per image); the
+//                          pack kernel takes one pad mode per image for that;
 //   * pad_nchw_kernel:     fp32 (B,C,h,w) -> (B,C,hp,wp), either mode;
 //   * rgba_unpack_kernel:  padded fp32 x_hat (+ alpha) -> ragged uint8 RGBA cropped to
 //                          (h_b, w_b): u8 = (uint8) clamp(x*255 + 0.5, 0, 255), the multiply and
@@ -43,7 +46,8 @@ __device__ __forceinline__ void ld_f4(const float* p, float (&v)[4]) {
 
 __global__ void __launch_bounds__(256)
 rgba_pack_kernel(const ImgDesc* __restrict__ descs, int hp, int wp, long long items, int mode,
-                 float* __restrict__ alpha, float* __restrict__ rgb, float* __restrict__ masked) {
+                 const int32_t* __restrict__ modes, float* __restrict__ alpha,
+                 float* __restrict__ rgb, float* __restrict__ masked) {
   const int wq = wp >> 2;
   const size_t plane = (size_t)hp * wp;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items;
@@ -57,7 +61,8 @@ rgba_pack_kernel(const ImgDesc* __restrict__ descs, int hp, int wp, long long it
     float v[4][4];  // [channel R,G,B,A][column]
     // an empty descriptor reads nothing and yields zeros (the host builds them checked)
     const bool ok = d.ptr && d.h > 0 && d.w > 0;
-    const bool rep = mode == RGBAC_PAD_REPLICATE;
+    // one mode for the batch, or one per image (rgbac_rgba_pack_modes)
+    const bool rep = (modes ? modes[b] : mode) == RGBAC_PAD_REPLICATE;
     const int sr = r < d.h ? r : d.h - 1;
     const bool row_in = ok && (rep || r < d.h);
     const uint8_t* row = reinterpret_cast<const uint8_t*>(d.ptr) + (long long)sr * d.row_stride_bytes;
@@ -85,6 +90,42 @@ rgba_pack_kernel(const ImgDesc* __restrict__ descs, int hp, int wp, long long it
       }
     }
   }
+}
+
+// grid (RGBAC_OPAQUE_BLOCKS, B): block k of image b looks at its share of the rectangle's
+// pixels (one dword per lane, adjacent lanes adjacent pixels of a row) and writes
+// scratch[b * RGBAC_OPAQUE_BLOCKS + k] = 1 if every alpha byte it saw is 255 (a block without
+// pixels writes 1; an empty descriptor 0).  An integer AND: no order to fix.
+__global__ void __launch_bounds__(256)
+rgba_opaque_kernel(const ImgDesc* __restrict__ descs, int32_t* __restrict__ scratch) {
+  const int b = blockIdx.y;
+  const ImgDesc d = descs[b];
+  const bool ok = d.ptr && d.h > 0 && d.w > 0;
+  int all = ok ? 1 : 0;
+  if (ok) {
+    const long long items = (long long)d.h * d.w;
+    const uint8_t* base = reinterpret_cast<const uint8_t*>(d.ptr);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items;
+         i += (long long)gridDim.x * 256) {
+      const int r = (int)(i / d.w), c = (int)(i - (long long)r * d.w);
+      const uchar4 p =
+          *reinterpret_cast<const uchar4*>(base + (long long)r * d.row_stride_bytes + 4 * (size_t)c);
+      all &= p.w == 255 ? 1 : 0;
+    }
+  }
+  all = __syncthreads_and(all);
+  if (threadIdx.x == 0) scratch[(size_t)b * gridDim.x + blockIdx.x] = all ? 1 : 0;
+}
+
+// one thread per image: the AND of its block flags
+__global__ void __launch_bounds__(256)
+rgba_opaque_final_kernel(int batch, const int32_t* __restrict__ scratch,
+                         int32_t* __restrict__ flags) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= batch) return;
+  int all = 1;
+  for (int k = 0; k < RGBAC_OPAQUE_BLOCKS; ++k) all &= scratch[(size_t)b * RGBAC_OPAQUE_BLOCKS + k];
+  flags[b] = all;
 }
 
 __global__ void __launch_bounds__(256)
@@ -251,9 +292,36 @@ extern "C" int rgbac_rgba_pack(int batch, const rgbac_image_desc* descs, int hp,
   RGBAC_REQUIRE(alpha || rgb || masked, "no output");
   const long long items = (long long)batch * hp * (wp >> 2);
   hipLaunchKernelGGL(rgba_pack_kernel, dim3(any_grid(items)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), descs, hp, wp, items, mode, alpha,
-                     rgb, masked);
+                     reinterpret_cast<hipStream_t>(stream), descs, hp, wp, items, mode,
+                     (const int32_t*)nullptr, alpha, rgb, masked);
   return check_launch("rgba_pack_kernel");
+}
+
+extern "C" int rgbac_rgba_pack_modes(int batch, const rgbac_image_desc* descs, int hp, int wp,
+                                     const int32_t* modes, float* alpha, float* rgb,
+                                     float* masked, void* stream) {
+  RGBAC_REQUIRE_CANVAS(batch, hp, wp);
+  RGBAC_REQUIRE(descs && modes, "null descriptor or mode pointer");
+  RGBAC_REQUIRE(alpha || rgb || masked, "no output");
+  const long long items = (long long)batch * hp * (wp >> 2);
+  hipLaunchKernelGGL(rgba_pack_kernel, dim3(any_grid(items)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), descs, hp, wp, items,
+                     (int)RGBAC_PAD_TRANSPARENT, modes, alpha, rgb, masked);
+  return check_launch("rgba_pack_kernel");
+}
+
+extern "C" int rgbac_rgba_opaque(int batch, const rgbac_image_desc* descs, int32_t* scratch,
+                                 int32_t* flags, void* stream) {
+  RGBAC_REQUIRE(batch > 0 && batch < 65536, "batch");
+  RGBAC_REQUIRE(descs && scratch && flags, "null pointer");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(rgba_opaque_kernel, dim3(RGBAC_OPAQUE_BLOCKS, batch), dim3(256), 0, st,
+                     descs, scratch);
+  int rc = check_launch("rgba_opaque_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(rgba_opaque_final_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch,
+                     scratch, flags);
+  return check_launch("rgba_opaque_final_kernel");
 }
 
 extern "C" int rgbac_pad_nchw(int batch, int channels, int h, int w, int hp, int wp, int mode,

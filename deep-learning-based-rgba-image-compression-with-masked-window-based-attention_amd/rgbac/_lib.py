@@ -94,6 +94,7 @@ class ImageDesc(ctypes.Structure):
 
 
 PAD_MODES = dict(transparent=0, replicate=1)   # enum rgbac_pad_mode
+OPAQUE_BLOCKS = 32                              # RGBAC_OPAQUE_BLOCKS
 
 _VP, _I32, _I64, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 _D = ctypes.c_double
@@ -186,6 +187,8 @@ SIGNATURES = {
     "rgbac_rgba_finish": [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
     # images of any size (pad / crop / region error around the codecs)
     "rgbac_rgba_pack": [_I32, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP],
+    "rgbac_rgba_opaque": [_I32, _VP, _VP, _VP, _VP],
+    "rgbac_rgba_pack_modes": [_I32, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP],
     "rgbac_pad_nchw": [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP],
     "rgbac_rgba_unpack": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP],
     "rgbac_region_error_blocks": [_I32, _I32],

@@ -275,32 +275,18 @@ def _upload(arr, device):
     return torch.from_numpy(arr).pin_memory().to(device, non_blocking=True)
 
 
-def encode_chunked_many(jobs, chunk):
-    """jobs: [(symbols, indexes, DeviceCdfTables, seg_lengths), ...] -> [bytes, ...], one
-    container per job.  All jobs share the host reads: the containers' sizes (a few bytes),
-    then one device->host copy of all finished containers."""
-    if not jobs:
-        return []
-    prep = []
-    dev = None
-    for sym, idx, tab, seg_lengths in jobs:
-        sym, idx = _dev_i32(sym, "symbols"), _dev_i32(idx, "indexes")
-        if not isinstance(tab, DeviceCdfTables):
-            raise TypeError("encode_chunked needs DeviceCdfTables")
-        if dev is None:
-            dev = sym.device
-        if idx.device != dev or sym.device != dev or tab.device != dev:
-            raise RuntimeError("symbols, indexes and tables must live on one device")
-        seg, _, table = _chunk_table(seg_lengths, chunk)
-        if sym.numel() != idx.numel() or sym.numel() != int(seg.sum()):
-            raise ValueError("symbols, indexes and seg_lengths disagree on the symbol count")
-        prep.append((sym, idx, tab, seg, table))
+def _encode_tables(prep, chunk):
+    """prep: [(symbols, indexes, DeviceCdfTables, table int64 (2, nchunks)), ...], checked device
+    tensors on one device -> per job one host int32 array: the chunks' word counts, then their
+    words, in table order.  One sizes and one encode launch per job; all jobs share the host
+    reads: the sizes (a few bytes), then one device->host copy of everything."""
+    dev = prep[0][0].device
     stream = _lib.stream_ptr(dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     queued = []
-    for sym, idx, tab, seg, table in prep:
+    for sym, idx, tab, table in prep:
         nch = table.shape[1]
-        tdev = _upload(table, dev)
+        tdev = _upload(np.ascontiguousarray(table), dev)
         counts = torch.empty(nch, dtype=torch.int32, device=dev)
         head = (sym.data_ptr(), idx.data_ptr(), int(sym.numel()), 0, tdev[0].data_ptr(),
                 tdev[1].data_ptr(), nch, int(chunk)) + tab.args()
@@ -321,10 +307,39 @@ def encode_chunked_many(jobs, chunk):
     out[pos:].copy_(err)
     host = out.cpu().numpy()                                          # the bytes: one copy
     _raise_code("encode_chunked", int(host[pos]))
-    blobs = []
-    for (_, _, _, seg, _), (p, nch, total) in zip(prep, spans):
-        blobs.append(_header(chunk, seg).tobytes() + host[p:p + nch + total].astype("<i4").tobytes())
-    return blobs
+    return [host[p:p + nch + total] for p, nch, total in spans]
+
+
+def _check_job(sym, idx, tab, dev):
+    sym, idx = _dev_i32(sym, "symbols"), _dev_i32(idx, "indexes")
+    if not isinstance(tab, DeviceCdfTables):
+        raise TypeError("encode_chunked needs DeviceCdfTables")
+    if dev is None:
+        dev = sym.device
+    if idx.device != dev or sym.device != dev or tab.device != dev:
+        raise RuntimeError("symbols, indexes and tables must live on one device")
+    if sym.numel() != idx.numel():
+        raise ValueError("symbols and indexes disagree on the symbol count")
+    return sym, idx, dev
+
+
+def encode_chunked_many(jobs, chunk):
+    """jobs: [(symbols, indexes, DeviceCdfTables, seg_lengths), ...] -> [bytes, ...], one
+    container per job.  All jobs share the host reads: the containers' sizes (a few bytes),
+    then one device->host copy of all finished containers."""
+    if not jobs:
+        return []
+    prep, segs = [], []
+    dev = None
+    for sym, idx, tab, seg_lengths in jobs:
+        sym, idx, dev = _check_job(sym, idx, tab, dev)
+        seg, _, table = _chunk_table(seg_lengths, chunk)
+        if sym.numel() != int(seg.sum()):
+            raise ValueError("symbols, indexes and seg_lengths disagree on the symbol count")
+        prep.append((sym, idx, tab, table))
+        segs.append(seg)
+    return [_header(chunk, seg).tobytes() + words.astype("<i4").tobytes()
+            for seg, words in zip(segs, _encode_tables(prep, chunk))]
 
 
 def encode_chunked(symbols, indexes, tables, seg_lengths, chunk=256):
@@ -393,20 +408,8 @@ def encode_chunked_host(symbols, indexes, tables, seg_lengths, chunk=256,
     seg, _, table = _chunk_table(seg_lengths, chunk)
     if s.size != i.size or s.size != int(seg.sum()):
         raise ValueError("symbols, indexes and seg_lengths disagree on the symbol count")
-    nch = table.shape[1]
-    counts = np.zeros(nch, dtype=np.int32)
-    total, err = ctypes.c_int64(0), ctypes.c_int32(0)
-    head = (s.ctypes.data, i.ctypes.data, int(s.size), 0, table[0].ctypes.data,
-            table[1].ctypes.data, nch, int(chunk)) + tab.args()
-    _lib.call("rgbac_rans_chunk_encode_host", *head, counts.ctypes.data, None, 0,
-              ctypes.byref(total), ctypes.byref(err))
-    _raise_code("encode_chunked_host", err.value)
-    payload = np.zeros(total.value, dtype=np.uint32)
-    _lib.call("rgbac_rans_chunk_encode_host", *head, counts.ctypes.data, payload.ctypes.data,
-              int(payload.size), ctypes.byref(total), ctypes.byref(err))
-    _raise_code("encode_chunked_host", err.value)
-    return (_header(chunk, seg).tobytes() + counts.astype("<i4").tobytes()
-            + payload.astype("<u4").tobytes())
+    return (_header(chunk, seg).tobytes()
+            + encode_table_host(s, i, tab, table, chunk).astype("<i4").tobytes())
 
 
 def decode_chunked_host(blob, indexes, tables, cdf_lengths=None, offsets=None):
@@ -427,3 +430,184 @@ def decode_chunked_host(blob, indexes, tables, cdf_lengths=None, offsets=None):
               *tab.args(), out.ctypes.data, ctypes.byref(err))
     _raise_code("chunked stream decode", err.value)
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Per-image containers from one batched pass (rgbac.rgbafile).  The chunk kernels address any
+# ranges of the flat symbol sequence they are given, so B images that share their segment
+# lengths are coded by one launch through one table ordered image-major, then segment, then
+# chunk; the host cuts the counts and the words into B containers, each byte for byte what
+# coding that image alone gives.  Decoding merges the files' tables the other way.  All of it
+# is host arithmetic on numpy arrays: the same functions drive the kernels and their *_host
+# twins.
+def image_major_table(seg_starts, seg_lengths, chunk):
+    """seg_starts int64 (B, nseg): where segment s of image b begins in the flat sequence the
+    coder is handed.  -> (table int64 (2, B * nch): each chunk's first symbol and length, image
+    b's nch chunks at [b * nch, (b + 1) * nch) in container order; nch)."""
+    seg, first, tab = _chunk_table(seg_lengths, chunk)
+    starts = np.asarray(seg_starts, dtype=np.int64).reshape(-1, seg.size)
+    base = np.concatenate([[0], np.cumsum(seg)[:-1]]).astype(np.int64)
+    which = np.repeat(np.arange(seg.size), np.diff(first))
+    local = tab[0] - base[which]                        # a chunk's offset inside its segment
+    nch = int(first[-1])
+    table = np.empty((2, starts.shape[0] * nch), dtype=np.int64)
+    table[0] = (starts[:, which] + local[None, :]).reshape(-1)
+    table[1] = np.tile(tab[1], starts.shape[0])
+    return table, nch
+
+
+def split_containers(words, nimages, seg_lengths, chunk):
+    """words: what one image-major pass wrote (every chunk's word count, then the chunks'
+    words back to back, in image_major_table order) -> [bytes, ...]: one container per image."""
+    seg, first, _ = _chunk_table(seg_lengths, chunk)
+    nch = int(first[-1])
+    words = np.asarray(words)
+    counts = words[:nimages * nch].astype(np.int64)
+    payload = words[nimages * nch:]
+    if int(counts.sum()) != payload.size:
+        raise ValueError("split_containers: the counts do not sum to the payload's length")
+    cut = np.concatenate([[0], np.cumsum(counts.reshape(nimages, nch).sum(axis=1))])
+    head = _header(chunk, seg).tobytes()
+    return [head + counts[b * nch:(b + 1) * nch].astype("<u4").tobytes()
+            + payload[int(cut[b]):int(cut[b + 1])].astype("<u4").tobytes()
+            for b in range(nimages)]
+
+
+def merged_decode_tables(layouts, seg_starts):
+    """layouts: one ChunkedLayout per file, all with the same seg_lengths; seg_starts int64
+    (B, nseg): where segment s of file b lands in the flat output.  -> (payload uint32: the
+    files' payloads back to back, meta int64 (3, nseg-major chunks): word offset into that
+    payload, first symbol, length; counts int32; first int64 (nseg + 1): segment s of ALL files
+    is meta[:, first[s]:first[s + 1]], file-major inside)."""
+    l0 = layouts[0]
+    nseg, B = l0.seg_lengths.size, len(layouts)
+    for lay in layouts:
+        if lay.seg_lengths.size != nseg or (lay.seg_lengths != l0.seg_lengths).any():
+            raise RuntimeError("chunked stream: the files of a group disagree on their segments")
+    starts = np.asarray(seg_starts, dtype=np.int64).reshape(B, nseg)
+    pbase = np.concatenate([[0], np.cumsum([lay.payload.size for lay in layouts])]).astype(np.int64)
+    meta, counts, first = [], [], [0]
+    for s in range(nseg):
+        for b, lay in enumerate(layouts):
+            c0, c1 = int(lay.first[s]), int(lay.first[s + 1])
+            meta.append(np.stack([pbase[b] + lay.offsets[c0:c1],
+                                  starts[b, s] + lay.table[0, c0:c1] - lay.seg_base[s],
+                                  lay.table[1, c0:c1]]))
+            counts.append(lay.counts[c0:c1])
+        first.append(first[-1] + sum(int(lay.first[s + 1] - lay.first[s]) for lay in layouts))
+    payload = np.concatenate([lay.payload for lay in layouts]).astype(np.uint32)
+    return (payload, np.ascontiguousarray(np.concatenate(meta, axis=1)),
+            np.concatenate(counts).astype(np.int32), np.asarray(first, dtype=np.int64))
+
+
+def _span(seg_starts, seg_lengths, lo, hi):
+    """(first symbol, symbol count) of the flat range that segments lo..hi-1 of all files cover."""
+    st = np.asarray(seg_starts, dtype=np.int64)[:, lo:hi]
+    base = int(st.min())
+    return base, int((st + np.asarray(seg_lengths, dtype=np.int64)[None, lo:hi]).max()) - base
+
+
+def encode_table_host(symbols, indexes, tables, table, chunk, cdf_lengths=None, offsets=None):
+    """The CPU twin of one sizes + encode pass through an arbitrary chunk table (int64
+    (2, nchunks)) -> int32 array: the counts, then the words (what split_containers takes)."""
+    s, i = _i32(symbols), _i32(indexes)
+    tab = CdfTables.of(tables, cdf_lengths, offsets)
+    table = np.ascontiguousarray(table, dtype=np.int64)
+    nch = table.shape[1]
+    counts = np.zeros(nch, dtype=np.int32)
+    total, err = ctypes.c_int64(0), ctypes.c_int32(0)
+    head = (s.ctypes.data, i.ctypes.data, int(s.size), 0, table[0].ctypes.data,
+            table[1].ctypes.data, nch, int(chunk)) + tab.args()
+    _lib.call("rgbac_rans_chunk_encode_host", *head, counts.ctypes.data, None, 0,
+              ctypes.byref(total), ctypes.byref(err))
+    _raise_code("encode_chunked_host", err.value)
+    payload = np.zeros(total.value, dtype=np.uint32)
+    _lib.call("rgbac_rans_chunk_encode_host", *head, counts.ctypes.data, payload.ctypes.data,
+              int(payload.size), ctypes.byref(total), ctypes.byref(err))
+    _raise_code("encode_chunked_host", err.value)
+    return np.concatenate([counts, payload.view(np.int32)])
+
+
+def decode_merged_host(layouts, seg_starts, indexes, tables, cdf_lengths=None, offsets=None):
+    """The CPU twin of MergedChunkedDecoder: decodes all segments of all files into one flat
+    int32 array laid out by seg_starts (``indexes`` in the same layout)."""
+    payload, meta, counts, first = merged_decode_tables(layouts, seg_starts)
+    i = _i32(indexes)
+    tab = CdfTables.of(tables, cdf_lengths, offsets)
+    base, nsym = _span(seg_starts, layouts[0].seg_lengths, 0, layouts[0].seg_lengths.size)
+    if base != 0 or i.size != nsym:
+        raise RuntimeError(f"chunked stream: the files hold symbols {base}..{base + nsym}, "
+                           f"{i.size} indexes given")
+    out = np.zeros(nsym, dtype=np.int32)
+    err = ctypes.c_int32(0)
+    K = max(lay.K for lay in layouts)
+    _lib.call("rgbac_rans_chunk_decode_host", payload.ctypes.data, int(payload.size),
+              meta[0].ctypes.data, counts.ctypes.data, i.ctypes.data, nsym, 0,
+              meta[1].ctypes.data, meta[2].ctypes.data, int(first[-1]), K, *tab.args(),
+              out.ctypes.data, ctypes.byref(err))
+    _raise_code("chunked stream decode", err.value)
+    return out
+
+
+def encode_image_major(jobs, chunk):
+    """jobs: [(symbols, indexes, DeviceCdfTables, seg_starts (B, nseg), seg_lengths), ...] ->
+    per job its B containers.  One sizes and one encode launch per job for all B images, the
+    host reads shared by all jobs (encode_chunked_many's two)."""
+    prep, cuts = [], []
+    dev = None
+    for sym, idx, tab, seg_starts, seg_lengths in jobs:
+        sym, idx, dev = _check_job(sym, idx, tab, dev)
+        table, _ = image_major_table(seg_starts, seg_lengths, chunk)
+        prep.append((sym, idx, tab, table))
+        cuts.append((np.asarray(seg_starts).reshape(-1, len(seg_lengths)).shape[0], seg_lengths))
+    return [split_containers(words, B, seg, chunk)
+            for (B, seg), words in zip(cuts, _encode_tables(prep, chunk))]
+
+
+class MergedChunkedDecoder:
+    """Decodes a group of containers that share their segment lengths as ONE launch per
+    segment range: the payloads are uploaded back to back with merged offset / start / length
+    tables (merged_decode_tables).  The interface latent_code expects of ``y_chunked``
+    (decode_segments, check); ``layouts`` are parsed, validated ChunkedLayouts."""
+
+    def __init__(self, layouts, seg_starts, device, err=None):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("MergedChunkedDecoder needs a GPU device (there is no CPU path; "
+                               "use decode_merged_host)")
+        payload, meta, counts, first = merged_decode_tables(layouts, seg_starts)
+        self.device, self.K = device, max(lay.K for lay in layouts)
+        self.seg_lengths = layouts[0].seg_lengths
+        self._starts = np.asarray(seg_starts, dtype=np.int64).reshape(len(layouts), -1)
+        self._first = first
+        self._payload = _upload(payload.view(np.int32), device)
+        self._meta = _upload(meta, device)
+        self._counts = _upload(counts, device)
+        self._err = err if err is not None else torch.zeros(1, dtype=torch.int32, device=device)
+
+    def decode_segments(self, lo, hi, indexes, tables, out=None):
+        """Segments lo..hi-1 of every file (device int32, the flat range they cover); no sync."""
+        if not 0 <= lo < hi <= self.seg_lengths.size:
+            raise ValueError("segment range")
+        idx = _dev_i32(indexes, "indexes")
+        if not isinstance(tables, DeviceCdfTables):
+            raise TypeError("decode_segments needs DeviceCdfTables")
+        base, nsym = _span(self._starts, self.seg_lengths, lo, hi)
+        if idx.numel() != nsym:
+            raise RuntimeError(f"chunked stream: segments {lo}..{hi - 1} cover {nsym} symbols, "
+                               f"{idx.numel()} indexes given")
+        if out is None:
+            out = torch.empty(nsym, dtype=torch.int32, device=self.device)
+        elif (out.dtype != torch.int32 or out.device != idx.device or out.numel() != nsym
+              or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous device int32 tensor of the segments' size")
+        c0, c1 = int(self._first[lo]), int(self._first[hi])
+        m = self._meta
+        _lib.call("rgbac_rans_chunk_decode", self._payload.data_ptr(), int(self._payload.numel()),
+                  m[0, c0:].data_ptr(), self._counts[c0:].data_ptr(), idx.data_ptr(), nsym, base,
+                  m[1, c0:].data_ptr(), m[2, c0:].data_ptr(), c1 - c0, self.K, *tables.args(),
+                  out.data_ptr(), self._err.data_ptr(), _lib.stream_ptr(self.device))
+        return out
+
+    def check(self):
+        _raise_code("chunked stream decode", int(self._err.item()))

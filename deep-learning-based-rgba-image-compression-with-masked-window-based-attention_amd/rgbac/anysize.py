@@ -87,24 +87,19 @@ def _canvas_tensor(t, channels, who, like=None):
         raise ValueError(f"{who}: shape {tuple(t.shape)} does not match {tuple(like.shape)}")
 
 
-def pack_rgba(images, pad="transparent", device="cuda"):
-    """images: list of (h, w, 4) uint8 arrays / tensors (decoded RGBA, CPU or GPU, any sizes).
-    Returns {"masked": (B,3,hp,wp), "alpha": (B,1,hp,wp), "rgb": (B,3,hp,wp), "sizes", "pad"}:
-    fp32 GPU planes on the batch's canvas, masked = where(alpha > 0, rgb, alpha).  One descriptor
-    upload and one launch for the batch."""
-    mode = _mode(pad)
+def _sources(images, device, who):
+    """images -> (device, sizes, descriptor entries, the device tensors behind them)."""
     images = list(images)
     if not images:
-        raise ValueError("pack_rgba: empty batch")
+        raise ValueError(f"{who}: empty batch")
     ts = []
     for im in images:
         t = torch.as_tensor(im)
         if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 4 or t.shape[0] < 1 or t.shape[1] < 1:
-            raise ValueError(f"pack_rgba: expected (H, W, 4) uint8 RGBA, got {tuple(t.shape)} {t.dtype}")
+            raise ValueError(f"{who}: expected (H, W, 4) uint8 RGBA, got {tuple(t.shape)} {t.dtype}")
         ts.append(t)
     dev = _gpu_device(device)
     sizes = [(int(t.shape[0]), int(t.shape[1])) for t in ts]
-    hp, wp = canvas(sizes)
     entries, keep = [], []
     for t, (h, w) in zip(ts, sizes):
         t = t.to(dev, non_blocking=True)
@@ -115,16 +110,70 @@ def pack_rgba(images, pad="transparent", device="cuda"):
             t = t.clone(memory_format=torch.contiguous_format)
         keep.append(t)
         entries.append((t.data_ptr(), h, w, t.stride(0)))
-    B = len(ts)
+    return dev, sizes, entries, keep
+
+
+def _pack(dev, sizes, entries, mode, modes):
+    """One pack launch onto the canvas of ``sizes``: ``mode`` for the batch, or a device int32
+    tensor ``modes`` with one pad mode per image."""
+    hp, wp = canvas(sizes)
+    B = len(sizes)
     descs = _upload_descs(entries, dev)
     masked = torch.empty((B, 3, hp, wp), device=dev)
     alpha = torch.empty((B, 1, hp, wp), device=dev)
     rgb = torch.empty((B, 3, hp, wp), device=dev)
-    _lib.call("rgbac_rgba_pack", B, descs.data_ptr(), hp, wp, mode, alpha.data_ptr(),
-              rgb.data_ptr(), masked.data_ptr(), _lib.stream_ptr(dev))
+    if modes is None:
+        _lib.call("rgbac_rgba_pack", B, descs.data_ptr(), hp, wp, mode, alpha.data_ptr(),
+                  rgb.data_ptr(), masked.data_ptr(), _lib.stream_ptr(dev))
+    else:
+        _lib.call("rgbac_rgba_pack_modes", B, descs.data_ptr(), hp, wp, modes.data_ptr(),
+                  alpha.data_ptr(), rgb.data_ptr(), masked.data_ptr(), _lib.stream_ptr(dev))
+    return {"masked": masked, "alpha": alpha, "rgb": rgb, "sizes": sizes}
+
+
+def pack_rgba(images, pad="transparent", device="cuda"):
+    """images: list of (h, w, 4) uint8 arrays / tensors (decoded RGBA, CPU or GPU, any sizes).
+    Returns {"masked": (B,3,hp,wp), "alpha": (B,1,hp,wp), "rgb": (B,3,hp,wp), "sizes", "pad"}:
+    fp32 GPU planes on the batch's canvas, masked = where(alpha > 0, rgb, alpha).  One descriptor
+    upload and one launch for the batch."""
+    mode = _mode(pad)
+    dev, sizes, entries, keep = _sources(images, device, "pack_rgba")
+    out = _pack(dev, sizes, entries, mode, None)
     # the sources (``keep``) and descriptors may be freed now: the caching allocator orders
     # their reuse after this launch on the same stream
-    return {"masked": masked, "alpha": alpha, "rgb": rgb, "sizes": sizes, "pad": pad}
+    out["pad"] = pad
+    return out
+
+
+def opaque_flags(images, device="cuda"):
+    """-> device int32 (B,): 1 where every alpha byte of the image is 255 (one launch for the
+    ragged batch, rgbac_rgba_opaque).  Nothing is read back here."""
+    dev, sizes, entries, keep = _sources(images, device, "opaque_flags")
+    return _opaque(dev, entries)
+
+
+def _opaque(dev, entries):
+    B = len(entries)
+    descs = _upload_descs(entries, dev)
+    scratch = torch.empty(B * _lib.OPAQUE_BLOCKS, dtype=torch.int32, device=dev)
+    flags = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.call("rgbac_rgba_opaque", B, descs.data_ptr(), scratch.data_ptr(), flags.data_ptr(),
+              _lib.stream_ptr(dev))
+    return flags
+
+
+def pack_rgba_modes(images, modes, device="cuda"):
+    """pack_rgba with one pad mode per image: ``modes`` a device int32 (B,) tensor of
+    rgbac_pad_mode values (1 replicates, anything else pads transparent, so opaque_flags'
+    result can be passed as it is) or a list of "transparent" / "replicate".  Bit-identical,
+    image by image, to pack_rgba with that image's mode."""
+    dev, sizes, entries, keep = _sources(images, device, "pack_rgba_modes")
+    if not isinstance(modes, torch.Tensor):
+        modes = torch.tensor([_mode(m) for m in modes], dtype=torch.int32).to(dev)
+    rt.check_gpu(modes)
+    if modes.dtype != torch.int32 or modes.numel() != len(sizes):
+        raise ValueError(f"pack_rgba_modes: need {len(sizes)} int32 pad modes")
+    return _pack(dev, sizes, entries, None, modes.contiguous())
 
 
 def pad_planes(t, pad="transparent"):

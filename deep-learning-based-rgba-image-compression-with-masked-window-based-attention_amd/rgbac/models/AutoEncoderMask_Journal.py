@@ -170,6 +170,23 @@ class AutoEncoder(_CompressionModelMixin, nn.Module):
         self.gaussian_conditional = GaussianConditional(None)
         self.compute_dtype = torch.float32
 
+    @property
+    def M(self):
+        """The latent width under the RGB model's name (the shared latent_code reads it)."""
+        return self.maskM
+
+    def compress(self, mask, *, coder="host", chunk=256):
+        """The alpha plane's bitstream (rgbac/models/_codec.py): the RGB model's compress over
+        EncoderMask; the same dict and stream formats."""
+        from ._codec import compress_mask
+        return compress_mask(self, mask, coder=coder, chunk=chunk)
+
+    def decompress(self, strings, shape, *, coder="host"):
+        """-> {"x_hat": (B,1,H,W) clamped to [0, 1]}, B = len(strings[1]), on the model's
+        device.  Pass the coder compress was called with."""
+        from ._codec import decompress_mask
+        return decompress_mask(self, strings, shape, coder=coder)
+
     def set_compute_dtype(self, dtype):
         assert dtype in (torch.float32, torch.bfloat16)
         self.compute_dtype = dtype

@@ -169,9 +169,15 @@ def compress(model, input, mask, coder="host", chunk=256):
         _, me = mask_pyramid(mask, 4)                            # EncMakeMask(mask) (:314)
         y = model.Encoder.nhwc(xf, me[1], me[2])                 # :315
         _, z_sym, y_sym, y_idx = latent_code(model, y=y)
-        if device_coder:
-            return _compress_device(model, z_sym, y_sym, y_idx, chunk)
-        z_host, ys_host, yi_host = z_sym.cpu(), y_sym.cpu(), y_idx.cpu()   # one sync
+    return _entropy_code(model, z_sym, y_sym, y_idx, device_coder, chunk)
+
+
+def _entropy_code(model, z_sym, y_sym, y_idx, device_coder, chunk):
+    """The symbols of one batch -> compress's dict (either coder); shared by both models."""
+    B = z_sym.shape[0]
+    if device_coder:
+        return _compress_device(model, z_sym, y_sym, y_idx, chunk)
+    z_host, ys_host, yi_host = z_sym.cpu(), y_sym.cpu(), y_idx.cpu()       # one sync
     eb = model.entropy_bottleneck
     C, zh, zw = z_host.shape[1:]
     z_idx = torch.arange(C, dtype=torch.int32).view(C, 1).expand(C, zh * zw).reshape(-1)
@@ -203,9 +209,10 @@ def _compress_device(model, z_sym, y_sym, y_idx, chunk):
             "coder": "device"}
 
 
-def _decompress_device(model, strings, zh, zw, mask):
+def _latent_device(model, strings, zh, zw, dev):
+    """The device coder's half of decompress: -> (YH, the y decoder whose check() reads the
+    shared error word once the synthesis is queued)."""
     eb, gc = model.entropy_bottleneck, model.gaussian_conditional
-    dev = mask.device
     B, C = len(strings[1]), eb.channels
     if len(strings[0]) != 1:
         raise RuntimeError("decompress: strings[0] must hold one y container")
@@ -223,6 +230,31 @@ def _decompress_device(model, strings, zh, zw, mask):
         for b, d in enumerate(z_decs):
             d.decode_segments(0, 1, z_idx, z_tab, out=z_sym[b])
         YH, _, _, _ = latent_code(model, z_sym=z_sym, y_chunked=y_dec)
+    return YH, y_dec
+
+
+def _latent_host(model, strings, zh, zw, dev):
+    """The host coder's half of decompress -> YH."""
+    eb = model.entropy_bottleneck
+    B = len(strings[1])
+    C = eb.channels
+    z_idx = torch.arange(C, dtype=torch.int32).view(C, 1).expand(C, zh * zw).reshape(-1)
+    z_tab = eb.tables()
+    z_sym = torch.empty((B, C, zh, zw), dtype=torch.int32)
+    for b, s in enumerate(strings[1]):                           # EntropyBottleneck.decompress
+        dec = RansDecoder()
+        dec.set_stream(s)
+        z_sym[b] = torch.from_numpy(dec.decode_stream_np(z_idx, z_tab)).view(C, zh, zw)
+    dec = RansDecoder()
+    dec.set_stream(strings[0][0])                                # :387-388
+    with torch.no_grad():
+        YH, _, _, _ = latent_code(model, z_sym=z_sym.to(dev), y_decoder=dec)
+    return YH
+
+
+def _decompress_device(model, strings, zh, zw, mask):
+    YH, y_dec = _latent_device(model, strings, zh, zw, mask.device)
+    with torch.no_grad():
         _, md = mask_pyramid(mask, 4)
         xh = model.Decoder.nhwc(YH, md[1], md[2])
         x_hat = rt.to_nchw(xh).clamp_(0, 1)
@@ -238,23 +270,51 @@ def decompress(model, strings, shape, mask, coder="host"):
     _check(model, mask)
     if device_coder:
         return _decompress_device(model, strings, int(shape[0]), int(shape[1]), mask)
-    eb = model.entropy_bottleneck
-    zh, zw = int(shape[0]), int(shape[1])
-    B = len(strings[1])
-    C = eb.channels
-    z_idx = torch.arange(C, dtype=torch.int32).view(C, 1).expand(C, zh * zw).reshape(-1)
-    z_tab = eb.tables()
-    z_sym = torch.empty((B, C, zh, zw), dtype=torch.int32)
-    for b, s in enumerate(strings[1]):                           # EntropyBottleneck.decompress
-        dec = RansDecoder()
-        dec.set_stream(s)
-        z_sym[b] = torch.from_numpy(dec.decode_stream_np(z_idx, z_tab)).view(C, zh, zw)
-    dec = RansDecoder()
-    dec.set_stream(strings[0][0])                                # :387-388
-    dev = mask.device
+    YH = _latent_host(model, strings, int(shape[0]), int(shape[1]), mask.device)
     with torch.no_grad():
-        YH, _, _, _ = latent_code(model, z_sym=z_sym.to(dev), y_decoder=dec)
         _, md = mask_pyramid(mask, 4)                            # DecMakeMask(mask) (:412)
         xh = model.Decoder.nhwc(YH, md[1], md[2])                # :414
         x_hat = rt.to_nchw(xh).clamp_(0, 1)
+    return {"x_hat": x_hat}
+
+
+def compress_mask(model, mask, coder="host", chunk=256):
+    """The alpha codec's compress: mask (B,1,H,W) -> compress's dict, the same stream formats as
+    the RGB codec's.  The reference's alpha model has a forward only
+    (models/AutoEncoderMask_Journal.py:248-316); this is the RGB model's compress (:312-371) over
+    that forward's transforms: EncoderMask, then the shared latent path (5 slices of 16
+    channels, each its own wave)."""
+    device_coder = _coder(coder)
+    _check(model, mask)
+    from .AutoEncoderMask_Journal import _run_seq, check_geometry
+    check_geometry(int(mask.shape[2]), int(mask.shape[3]))
+    with torch.no_grad():
+        y = _run_seq(model.EncoderMask, rt.to_nhwc(mask.contiguous().float(), model.compute_dtype))
+        _, z_sym, y_sym, y_idx = latent_code(model, y=y)
+    return _entropy_code(model, z_sym, y_sym, y_idx, device_coder, chunk)
+
+
+def mask_synthesis(model, YH):
+    """DecoderMask and the clamp -> x_hat (B,1,H,W) fp32 in [0, 1]."""
+    from .AutoEncoderMask_Journal import _run_seq
+    with torch.no_grad():
+        return rt.to_nchw(_run_seq(model.DecoderMask, YH)).clamp_(0, 1)
+
+
+def decompress_mask(model, strings, shape, coder="host"):
+    """The alpha codec's decompress -> {"x_hat": (B,1,H,W) clamped to [0, 1]}, on the model's
+    device; B = len(strings[1])."""
+    device_coder = _coder(coder)
+    dev = next(model.parameters()).device
+    if dev.type != "cuda":
+        raise RuntimeError("rgbac: this module runs on the GPU (HIP) only; the model is on "
+                           f"{dev}.")
+    _check(model)
+    zh, zw = int(shape[0]), int(shape[1])
+    if device_coder:
+        YH, y_dec = _latent_device(model, strings, zh, zw, dev)
+        x_hat = mask_synthesis(model, YH)
+        y_dec.check()
+    else:
+        x_hat = mask_synthesis(model, _latent_host(model, strings, zh, zw, dev))
     return {"x_hat": x_hat}

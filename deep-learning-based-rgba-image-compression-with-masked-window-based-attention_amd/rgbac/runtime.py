@@ -289,19 +289,63 @@ def tune_cache():
 
 
 _FIXED = [0]
+_PER_IMAGE = [0]
 
 
 @contextlib.contextmanager
-def fixed_tiles():
+def fixed_tiles(per_image=False):
     """Within this context every conv launch takes its tile / split-K from the shape rule
     alone (no timing-based autotune, tune cache neither read nor written).  The bitstream
     path needs bit-identical mu / sigma in compress and decompress, whichever process (and
-    tuning history) runs them: a different tile or split-K changes the fp32 summation order."""
+    tuning history) runs them: a different tile or split-K changes the fp32 summation order.
+
+    ``per_image=True``: the rule sees ONE image's geometry (the launch as if its batch were 1),
+    so the choice is the same whatever the batch size -- what a stream that must decode alone
+    or in any batch needs (rgbac.rgbafile).  It stays on for every fixed_tiles() nested inside
+    (latent_code's own), and is the plain rule's answer at B = 1."""
     _FIXED[0] += 1
+    _PER_IMAGE[0] += 1 if per_image else 0
     try:
         yield
     finally:
         _FIXED[0] -= 1
+        _PER_IMAGE[0] -= 1 if per_image else 0
+
+
+def _one_image(pr):
+    """A copy of a Prepared whose ABI record and M describe one image of its batch (what the
+    per-image rule and the library's validation are asked about; never launched)."""
+    q = Prepared()
+    for name in Prepared.__slots__:
+        if hasattr(pr, name):
+            setattr(q, name, getattr(pr, name))
+    q.a = type(pr.a).from_buffer_copy(pr.a)
+    q.mgrid = pr.mgrid // pr.a.batch
+    q.a.batch = 1
+    return q
+
+
+def rule_choice(preps, per_image=False):
+    """The shape rule's (tile, ksplit) for these grouped convs: what launch() uses under
+    fixed_tiles().  Pure host code (the library is only asked to validate).  With
+    ``per_image`` every input is one image's: M = mgrid / batch, and the GAUSS branch's
+    candidates are validated for a batch of 1; the other inputs are dtype, channels, taps and
+    the group count.  The choice must also take the real batch -- if not, that is an error,
+    never another choice."""
+    real = preps
+    if per_image:
+        preps = [_one_image(pr) for pr in preps]
+    p0 = preps[0]
+    if p0.a.act == ACT["gauss"]:
+        choice = min(candidates(preps), key=lambda c: TILES[c[0]][1])
+    else:
+        choice = _heuristic(p0.mgrid * p0.nphase * len(preps),
+                            max(pr.pk.cout for pr in preps), max(pr.nst for pr in preps))
+    choice = resolve_choice(choice, preps)
+    if per_image and not _choice_valid(choice[0], real, choice[1]):
+        raise RuntimeError(f"rgbac: the per-image tile rule chose {choice} for {real[0].desc}, "
+                           "which this batch size does not take")
+    return choice
 
 
 def load_tune_cache(path):
@@ -712,6 +756,8 @@ def launch(preps, force=None):
     choice = None if fixed else (FORCE if (FORCE and not gauss) else _tune_cache.get(key))
     if force is not None:
         choice = tuple(force)
+    if choice is None and fixed and _PER_IMAGE[0] > 0:
+        choice = rule_choice(preps, per_image=True)      # one image's geometry, never B
     if choice is None:
         mtot = p0.mgrid * p0.nphase * n
         cout = max(pr.pk.cout for pr in preps)

@@ -696,6 +696,22 @@ int rgbac_rgba_pack(int batch, const rgbac_image_desc* descs, int hp, int wp, in
                     float* alpha, float* rgb, float* masked, void* stream);
 int rgbac_pad_nchw(int batch, int channels, int h, int w, int hp, int wp, int mode,
                    const float* x, float* out, void* stream);
+/* Per-image opacity and pad mode (the RGBA file encoder: an opaque image is padded by
+ * replication and gets no alpha stream, a batch may mix both kinds).
+ * rgbac_rgba_opaque: flags[b] = 1 if every alpha byte inside image b's rectangle is 255, else 0
+ *   (0 for an empty descriptor), for the ragged batch as rgbac_rgba_pack takes it.  DEVICE
+ *   int32 flags[batch]; scratch: DEVICE int32[batch * RGBAC_OPAQUE_BLOCKS], no initial contents
+ *   needed.  Integer AND only: bit-reproducible.
+ * rgbac_rgba_pack_modes: rgbac_rgba_pack with a DEVICE array of `batch` pad modes instead of
+ *   one: image b replicates where modes[b] == RGBAC_PAD_REPLICATE and pads transparent for any
+ *   other value (so rgbac_rgba_opaque's flags can be passed as they are).  The same kernel:
+ *   bit-identical to rgbac_rgba_pack with image b's mode. */
+#define RGBAC_OPAQUE_BLOCKS 32
+int rgbac_rgba_opaque(int batch, const rgbac_image_desc* descs, int32_t* scratch,
+                      int32_t* flags, void* stream);
+int rgbac_rgba_pack_modes(int batch, const rgbac_image_desc* descs, int hp, int wp,
+                          const int32_t* modes, float* alpha, float* rgb, float* masked,
+                          void* stream);
 int rgbac_rgba_unpack(int batch, const rgbac_image_desc* descs, int hp, int wp,
                       const float* x_hat, const float* alpha, int zero_transparent,
                       void* stream);
