@@ -93,6 +93,12 @@ class ImageDesc(ctypes.Structure):
                 ("row_stride_bytes", ctypes.c_int64)]
 
 
+class SsimAnyDesc(ctypes.Structure):
+    """rgbac_ssim_any_desc"""
+    _fields_ = [("h", ctypes.c_int32), ("w", ctypes.c_int32), ("tiles_x", ctypes.c_int32),
+                ("ntiles", ctypes.c_int32)]
+
+
 PAD_MODES = dict(transparent=0, replicate=1)   # enum rgbac_pad_mode
 OPAQUE_BLOCKS = 32                              # RGBAC_OPAQUE_BLOCKS
 
@@ -208,6 +214,17 @@ SIGNATURES = {
                                     _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP],
     "rgbac_msssim_combine_bwd": [_I32, _I32, _VP, _VP, _VP, _VP, _I32, _VP, _VP],
     "rgbac_masked_msssim_combine_bwd": [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _I32, _VP, _VP],
+    # ragged MS-SSIM (evaluation) and per-image bits
+    "rgbac_ssim_any_tiles": [_I32, _I32, _I32],
+    "rgbac_ssim_any_partial_floats": [_I32, _I32, _I32, _I32],
+    "rgbac_ssim_any_level": [_I32, _I32, _I32, _I32, _I32, _VP, _I32, _VP, _VP, _VP, _VP, _F, _F,
+                             _VP, _VP],
+    "rgbac_avgpool2_any": [_I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                           _VP],
+    "rgbac_ssim_any_reduce": [_I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I64, _VP,
+                              _VP, _VP, _VP],
+    "rgbac_image_bits_blocks": [_I64, _I32],
+    "rgbac_image_bits": [_I32, _I64, _I32, _VP, _VP, _VP, _VP],
     "rgbac_pmf_to_quantized_cdf": [_VP, _I32, _I32, _VP],
     "rgbac_rans_encoder_create": [ctypes.POINTER(ctypes.c_void_p)],
     "rgbac_rans_encoder_destroy": [_VP],
@@ -240,7 +257,8 @@ SIGNATURES = {
                                      ctypes.POINTER(ctypes.c_int32)],
 }
 _RESTYPE = {"rgbac_last_error": ctypes.c_char_p, "rgbac_rans_encoder_bound": ctypes.c_int64,
-            "rgbac_winattn_block_workspace": ctypes.c_int64}
+            "rgbac_winattn_block_workspace": ctypes.c_int64,
+            "rgbac_ssim_any_partial_floats": ctypes.c_int64}
 
 _lib = None
 

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from . import runtime as rt
-from .rgba import rgba_forward
+from .rgba import _chain, rgba_forward
 
 TILE = 64
 
@@ -309,3 +309,57 @@ def rgba_forward_any(masknet, net, images, pad="transparent"):
                        "recon_alpha": recon_alpha, "mse": mse_c, "bpp_total": bpp_c,
                        "bpp_mask": out_mask[2]}}
 
+
+
+@torch.no_grad()
+def rgba_eval_any(masknet, net, images, msssim=True, masked_msssim=False):
+    """The reference's test loop (trainRGB.py:282-317) for a list of decoded RGBA images of any
+    sizes in ONE batched pass: every image gets the three figures the loop prints for it -- its
+    own rate, PSNR and MS-SSIM -- as (B,) device tensors.
+
+    Padding is decided per image on the device (rgbac_rgba_opaque; the flags are not read back):
+    an opaque image is replicated, so its alpha stays all ones; the others are padded
+    transparent.  The chain is rgba_forward's (masknet -> recon_alpha -> RGB net -> clamp) with
+    both nets' per-image bits (``per_image=``).  Returns
+      "bpp_rgb" = (y_bits + z_bits) / (h_b w_b) of the RGB net, "bpp_alpha" the same of masknet,
+      "bpp" = bpp_rgb + (opaque_b ? 0 : bpp_alpha)   (:299-302, decided per image),
+      "y_bits" / "z_bits" / "y_bits_alpha" / "z_bits_alpha": (B,) fp64,
+      "mse" / "psnr" / "sse" / "n": region_error over the real rectangle and true alpha > 0,
+      "ms_ssim" = ms_ssim_any(masked, x_hat, sizes, data_range=1) (:311), "ms_ssim_db" =
+      -10 log10(1 - ms_ssim) (:312)   [msssim=True],
+      "masked_ms_ssim": masked_ms_ssim_any with the true alpha as the mask [masked_msssim=True],
+      "rgba": the uint8 reconstructions, "sizes", "opaque": device int32 (B,), "canvas" (as
+      rgba_forward_any's; its bpp_total stays rgba_forward's batch-wide figure).
+    An image's bits are all the bits of its canvas latents (what a coder spends), divided by its
+    real pixel count.  With the MS-SSIM figures on, every side must exceed 160 (ValueError)."""
+    dev = next(net.parameters()).device
+    dev, sizes, entries, keep = _sources(images, dev, "rgba_eval_any")
+    if msssim or masked_msssim:
+        from .metrics.any_size import level_table, masked_ms_ssim_any, ms_ssim_any
+        level_table(sizes, 5, 11)                    # too small an image: raise before any launch
+    opaque = _opaque(dev, entries)
+    p = _pack(dev, sizes, entries, None, opaque)
+    bm, br = {}, {}
+    img, recon_alpha, mse_c, bpp_c, _, out_mask = _chain(masknet, net, p["masked"], p["alpha"],
+                                                        bits_mask=bm, bits_rgb=br)
+    rgba = unpack_rgba(img, recon_alpha, sizes)
+    mse, psnr, sse, n = region_error(p["masked"], img, sizes, mask=p["alpha"])
+    npix = torch.tensor([h * w for h, w in sizes], dtype=torch.float64).to(dev)
+    bpp_rgb = (br["y_bits"] + br["z_bits"]) / npix
+    bpp_alpha = (bm["y_bits"] + bm["z_bits"]) / npix
+    bpp = bpp_rgb + torch.where(opaque == 1, torch.zeros_like(bpp_alpha), bpp_alpha)
+    out = {"rgba": rgba, "mse": mse, "psnr": psnr, "sse": sse, "n": n,
+           "bpp": bpp.float(), "bpp_rgb": bpp_rgb.float(), "bpp_alpha": bpp_alpha.float(),
+           "y_bits": br["y_bits"], "z_bits": br["z_bits"],
+           "y_bits_alpha": bm["y_bits"], "z_bits_alpha": bm["z_bits"],
+           "sizes": sizes, "opaque": opaque,
+           "canvas": {"masked": p["masked"], "alpha": p["alpha"], "x_hat": img,
+                      "recon_alpha": recon_alpha, "mse": mse_c, "bpp_total": bpp_c,
+                      "bpp_mask": out_mask[2]}}
+    if msssim:
+        out["ms_ssim"] = ms_ssim_any(p["masked"], img, sizes, data_range=1.0)
+        out["ms_ssim_db"] = -10.0 * torch.log10(1.0 - out["ms_ssim"])
+    if masked_msssim:
+        out["masked_ms_ssim"] = masked_ms_ssim_any(p["masked"], img, p["alpha"], sizes,
+                                                   data_range=1.0)
+    return out

@@ -192,12 +192,18 @@ class AutoEncoder(_CompressionModelMixin, nn.Module):
         self.compute_dtype = dtype
         return self
 
-    def forward(self, mask, *, noise_z=None, noise_y=None, debug=None):
+    def forward(self, mask, *, noise_z=None, noise_y=None, debug=None, per_image=None):
+        """``per_image``: a dict; the evaluation forward fills it with "y_bits" and "z_bits",
+        (B,) fp64 -- every image's own share of the bits behind the returned bpp (latent_path).
+        Absent, the forward launches exactly what it launches without this argument."""
         rt.check_gpu(mask)
         B, _, H, W = mask.shape
         check_geometry(H, W)
         if debug is None and torch.is_grad_enabled() and \
                 any(p.requires_grad for p in self.parameters()):
+            if per_image is not None:
+                raise ValueError("per_image= is an evaluation option: call the model under "
+                                 "torch.no_grad()")
             # training step (trainmask.py:165-198): autograd graph over the HIP kernels
             from ..train_forward import mask_forward_train
             return mask_forward_train(self, mask, noise_z, noise_y)
@@ -205,7 +211,8 @@ class AutoEncoder(_CompressionModelMixin, nn.Module):
         with torch.no_grad():
             m = mask.contiguous().float()
             y = _run_seq(self.EncoderMask, rt.to_nhwc(m, dt))
-            yh, ypart, zpart = latent_path(self, y, self.training, noise_z, noise_y, debug)
+            yh, ypart, zpart = latent_path(self, y, self.training, noise_z, noise_y, debug,
+                                           per_image=per_image)
             xh = _run_seq(self.DecoderMask, yh)
             # x_hat's NCHW copy written by the loss pass (was a separate rgbac_nhwc_to_nchw)
             x_hat = torch.empty((B, xh.C, H, W), dtype=torch.float32, device=m.device)

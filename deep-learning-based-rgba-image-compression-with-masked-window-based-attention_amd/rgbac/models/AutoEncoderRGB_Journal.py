@@ -209,12 +209,18 @@ class AutoEncoder(_CompressionModelMixin, nn.Module):
         return self
 
     def forward(self, input, mask, reconmask, me1, me2, me3, me4, *, noise_z=None,
-                noise_y=None, debug=None):
+                noise_y=None, debug=None, per_image=None):
+        """``per_image``: a dict; the evaluation forward fills it with "y_bits" and "z_bits",
+        (B,) fp64 -- every image's own share of the bits behind the returned bpp (latent_path).
+        Absent, the forward launches exactly what it launches without this argument."""
         rt.check_gpu(input, mask, reconmask, me2, me3)
         B, _, H, W = input.shape
         check_geometry(H, W)
         if debug is None and torch.is_grad_enabled() and \
                 any(p.requires_grad for p in self.parameters()):
+            if per_image is not None:
+                raise ValueError("per_image= is an evaluation option: call the model under "
+                                 "torch.no_grad()")
             # training step (trainRGB.py:178-198): autograd graph over the HIP kernels
             from ..train_forward import rgb_forward_train
             return rgb_forward_train(self, input, mask, reconmask, me2, me3, noise_z, noise_y)
@@ -238,7 +244,7 @@ class AutoEncoder(_CompressionModelMixin, nn.Module):
                 xf = rt.to_nhwc(x, dt)
             y = self.Encoder.nhwc(xf, me2, me3)                                  # :217
             yh, ypart, zpart = latent_path(self, y, self.training, noise_z, noise_y, debug,
-                                           ypart=ypart)
+                                           ypart=ypart, per_image=per_image)
             main.wait_stream(side)
             xh = self.Decoder.nhwc(yh, md[1], md[2])                              # :273
             # x_hat's NCHW copy written by the loss pass itself (one read of x_hat)

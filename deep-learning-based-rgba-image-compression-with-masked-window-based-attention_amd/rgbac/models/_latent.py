@@ -115,10 +115,36 @@ def ypart_slots(model, B, h, w):
     return model.num_slices, -(-(B * h * w) // 32)
 
 
-def latent_path(model, y, training=False, noise_z=None, noise_y=None, debug=None, ypart=None):
+def image_bits(lik, batch, segments=1):
+    """Per-image rate (rgbac_image_bits): ``lik`` fp32, contiguous, laid out
+    [segments][batch][n] -> (batch,) fp64 sums of the forward's own fp32 bits term
+    clamp(-log(lik + 1e-10) / ln 2, 0, 50), segments then elements, in a fixed order."""
+    rt.check_gpu(lik)
+    if lik.dtype != torch.float32 or not lik.is_contiguous():
+        raise ValueError("image_bits: a contiguous fp32 likelihood tensor is needed")
+    batch, segments = int(batch), int(segments)
+    if batch < 1 or segments < 1 or lik.numel() == 0 or lik.numel() % (batch * segments):
+        raise ValueError(f"image_bits: {lik.numel()} likelihoods do not split into {segments} "
+                         f"segments of {batch} images")
+    n = lik.numel() // (batch * segments)
+    dev = lik.device
+    nblk = _lib.load().rgbac_image_bits_blocks(n, segments)
+    scratch = torch.empty((batch * nblk,), dtype=torch.float64, device=dev)
+    bits = torch.empty((batch,), dtype=torch.float64, device=dev)
+    _lib.call("rgbac_image_bits", batch, n, segments, lik.data_ptr(), scratch.data_ptr(),
+              bits.data_ptr(), _lib.stream_ptr(dev))
+    return bits
+
+
+def latent_path(model, y, training=False, noise_z=None, noise_y=None, debug=None, ypart=None,
+                per_image=None):
     """y: Feat (B,h,w,M) -> (YH Feat, ybits fp64 partials, zbits fp64 partials).
     ``ypart``: a zeroed fp64 (slices, slots) buffer (ypart_slots) for the bits partials, e.g.
-    zero-filled by the forward's prologue launch; allocated and zeroed here when None."""
+    zero-filled by the forward's prologue launch; allocated and zeroed here when None.
+    ``per_image``: a dict that receives "y_bits" and "z_bits", (B,) fp64 each: the GAUSS
+    epilogues and eb_forward also store the likelihoods whose bits they sum, and image_bits adds
+    them per image (slices in slice order).  The launches are otherwise the same as without
+    it -- unlike ``debug``, which re-runs convs."""
     dev, dt = y.t.device, y.t.dtype
     ns, msup = model.num_slices, model.max_support_slices
     M = y.C
@@ -128,7 +154,7 @@ def latent_path(model, y, training=False, noise_z=None, noise_y=None, debug=None
     z_hat = rt.new_feat(z.B, z.H, z.W, z.C, dt, dev)
     zpart = torch.empty(reduce_blocks(z.B * z.H * z.W * z.C), dtype=torch.float64, device=dev)
     zlik = None
-    if debug is not None:
+    if debug is not None or per_image is not None:
         zlik = torch.empty((z.B, z.H, z.W, z.C), dtype=torch.float32, device=dev)
     nz = None
     if training:
@@ -145,6 +171,11 @@ def latent_path(model, y, training=False, noise_z=None, noise_y=None, debug=None
         ypart = torch.zeros(ypart_slots(model, B, h, w), dtype=torch.float64, device=dev)
     assert tuple(ypart.shape) == ypart_slots(model, B, h, w) and ypart.dtype == torch.float64
     liks = [None] * ns
+    ylik = None
+    if per_image is not None:
+        # the slices' likelihoods side by side, [slice][B][h w cs]: one image_bits launch pair
+        ylik = torch.empty((ns, B, h, w, cs), dtype=torch.float32, device=dev)
+        liks = [ylik[i] for i in range(ns)]
     musig = [None] * ns
     waves = [[i] for i in range(min(msup, ns))]
     if ns > msup:
@@ -201,6 +232,9 @@ def latent_path(model, y, training=False, noise_z=None, noise_y=None, debug=None
                  (main, ev_cc, ev_lrp, Pm, Ps, Plrp) if pre_ok else None)
     if pre_ok:
         main.wait_stream(side)                 # join the side stream (graph capture needs it)
+    if per_image is not None:
+        per_image["y_bits"] = image_bits(ylik, B, segments=ns)
+        per_image["z_bits"] = image_bits(zlik, z.B)
     if debug is not None:
         debug.update(z=z, z_hat=z_hat, z_lik=zlik, y_lik=liks, latent_means=means,
                      latent_scales=scales, y_hat=YH, musigma=musig)
@@ -253,7 +287,7 @@ def _slice_waves(model, waves, y, YH, means, scales, Cm, cs, B, h, w, dt, dev, t
             if training:
                 nyi = (noise_y[..., i * cs:(i + 1) * cs].contiguous() if noise_y is not None
                        else torch.rand((B, h, w, cs), device=dev) - 0.5)
-            if debug is not None:
+            if debug is not None and liks[i] is None:
                 liks[i] = torch.empty((B, h, w, cs), dtype=torch.float32, device=dev)
             preps.append(rt.prepare(pk, [t2[j].src(), t2[k + j].src()], out=pre, act="gauss",
                                     res1=(y, i * cs), aux0=nyi, aux1=liks[i], partial=ypart[i]))

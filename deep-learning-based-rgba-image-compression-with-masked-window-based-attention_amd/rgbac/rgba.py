@@ -54,13 +54,27 @@ def rgba_forward(masknet, net, masked_input, mask, msssim=False):
     psnr = 10*log10(1/mse) (:306), and out_mask is the alpha codec's own 5-tuple.  With
     msssim=True a 7th element is ms_ssim(masked_input, clipped image, data_range=1) (:311),
     computed by the HIP metric kernels."""
+    img, recon_mask, mse, bpp_total, psnr, out_mask = _chain(masknet, net, masked_input, mask)
+    if msssim:
+        from .metrics.ms_ssim_torch import ms_ssim
+        return (img, recon_mask, mse, bpp_total, psnr, out_mask,
+                ms_ssim(masked_input, img, data_range=1.0, size_average=True))
+    return img, recon_mask, mse, bpp_total, psnr, out_mask
+
+
+def _chain(masknet, net, masked_input, mask, bits_mask=None, bits_rgb=None):
+    """rgba_forward's launches: masknet -> recon_alpha -> RGB net -> clamp and scalars.
+    ``bits_mask`` / ``bits_rgb``: dicts handed to the two nets as ``per_image=`` (the per-image
+    bits of rgbac.anysize.rgba_eval_any); absent, the nets are called as always."""
     rt.check_gpu(masked_input, mask)
     mask = mask.contiguous().float()
     levels = mask_pyramid(mask, 6)[1]                        # EncMakeMask(mask)  (:283)
-    out_mask = masknet(mask)                                  # masknet(mask)      (:284)
+    kw_m = {} if bits_mask is None else {"per_image": bits_mask}
+    kw_r = {} if bits_rgb is None else {"per_image": bits_rgb}
+    out_mask = masknet(mask, **kw_m)                          # masknet(mask)      (:284)
     flag = torch.empty((1,), dtype=torch.int32, device=mask.device)
     recon_mask = _recon(out_mask[0], True, mask, flag)        # :285-287 (+ :300 flag)
-    x_hat, mse, bpp = net(masked_input, mask, recon_mask, *levels[:4])[:3]   # :289
+    x_hat, mse, bpp = net(masked_input, mask, recon_mask, *levels[:4], **kw_r)[:3]   # :289
     img = torch.empty_like(x_hat)
     bpp_total = torch.empty((), dtype=torch.float32, device=x_hat.device)
     psnr = torch.empty((), dtype=torch.float32, device=x_hat.device)
@@ -68,8 +82,4 @@ def rgba_forward(masknet, net, masked_input, mask, msssim=False):
     _lib.call("rgbac_rgba_finish", x_hat.numel(), x_hat.data_ptr(), img.data_ptr(),
               bpp_f.data_ptr(), bppm_f.data_ptr(), flag.data_ptr(), mse_f.data_ptr(),
               bpp_total.data_ptr(), psnr.data_ptr(), _lib.stream_ptr(x_hat.device))
-    if msssim:
-        from .metrics.ms_ssim_torch import ms_ssim
-        return (img, recon_mask, mse, bpp_total, psnr, out_mask,
-                ms_ssim(masked_input, img, data_range=1.0, size_average=True))
     return img, recon_mask, mse, bpp_total, psnr, out_mask

@@ -791,6 +791,71 @@ int rgbac_masked_msssim_combine_bwd(int levels, int batch, int channels, const f
                                     const float* ssim_last, const float* weights,
                                     const float* grad, int grad_is_mean, float* u, void* stream);
 
+/* Ragged MS-SSIM / masked MS-SSIM (csrc/msssim_any.hip), evaluation only: the two metrics
+ * above for a batch of images of different sizes on one canvas (image b = the top-left
+ * h_b x w_b of its planes), each image scored as the reference scores it alone.  fp32 NCHW.
+ * Geometry: level 0 of image b is (h_b, w_b), level l+1 is ((h + 2(h%2) - 2)/2 + 1,
+ *   (w + 2(w%2) - 2)/2 + 1) (ms_ssim_torch.py:183-185 on that image); level l's planes are
+ *   (B, C, Hc_l, Wc_l) with Hc_l / Wc_l the largest image's; level 0 is the canvas itself, read
+ *   in place.  The host computes this and uploads ONE table descs[levels][batch] of
+ *   rgbac_ssim_any_desc (h, w: the image's size at that level; tiles_x, ntiles: the 16 x 16
+ *   tile grid of its valid map (h-ws+1) x (w-ws+1), for the host's own sizing -- the kernels
+ *   derive both from h, w and clamp h, w to the plane, so no table content makes them read or
+ *   write outside the planes and the scratch as sized below).
+ * rgbac_ssim_any_tiles: tile count of an h x w image's valid map (0 if smaller than the window).
+ * rgbac_ssim_any_partial_floats: floats of one level's tile partials (masked: 3 per tile, else
+ *   2) for max_tiles = the largest image's tile count at that level.
+ * rgbac_ssim_any_level: one launch = one scale of the whole batch; descs: that level's `batch`
+ *   entries; x, y (B, C, hc, wc); mask (B, 1, hc, wc) or NULL.  rgbac_ssim_level's tile
+ *   arithmetic with image b's own valid map as the output bound; grid = max_tiles x B*C, a
+ *   block past its image's tiles writes nothing.  With a mask: the level's (mask > 0) and
+ *   x * m, y * m (rgbac_masked_apply) are applied while loading, and an output is kept where
+ *   the mask NEAREST-resized from (h, w) to the valid map is nonzero (rgbac_masked_ssim_level,
+ *   with the image's own sizes).  partials[(plane * max_tiles + tile) * (2 | 3)].
+ * rgbac_avgpool2_any: one launch pools all planes of x and y (and the mask) of a level into
+ *   (.., hc_out, wc_out): out[oy][ox] = (sum of in[2 oy - h%2 + dy][2 ox - w%2 + dx]) / 4 with
+ *   image b's h, w; a tap outside the IMAGE's rectangle contributes 0 (not the plane's: row h
+ *   of an odd-h image is padding in the reference, other data on the canvas).  Outputs outside
+ *   the image's next-level rectangle are written 0.  descs: the INPUT level's entries.  With a
+ *   mask, x and y are multiplied by (mask > 0) and the mask is binarised before pooling.
+ * rgbac_ssim_any_reduce: one launch for all levels: per (level, image) that image's own tile
+ *   partials in (channel, tile) order, in double, / (C * valid pixels) -> ssim_out / cs_out
+ *   [level * B + b]; masked: per (level, image, channel), sum / ((float)count + 1e-10) ->
+ *   [(level * B + b) * C + c].  plane_h / plane_w / max_tiles / partial_offsets: HOST arrays of
+ *   `levels` (<= 8) entries, offsets in floats into partials (partial_floats in all).
+ * The last step is rgbac_msssim_combine / rgbac_masked_msssim_combine on those tables.
+ * No atomics, fixed order: an image's value depends on its own pixels and size only. */
+typedef struct rgbac_ssim_any_desc {
+  int32_t h, w;              /* the image's size at this level */
+  int32_t tiles_x, ntiles;   /* 16 x 16 tiles of its valid map: per row, in all */
+} rgbac_ssim_any_desc;
+int rgbac_ssim_any_tiles(int h, int w, int win_size);
+int64_t rgbac_ssim_any_partial_floats(int batch, int channels, int max_tiles, int masked);
+int rgbac_ssim_any_level(int batch, int channels, int hc, int wc, int win_size,
+                         const rgbac_ssim_any_desc* descs, int max_tiles, const float* x,
+                         const float* y, const float* mask, const float* win, float c1, float c2,
+                         float* partials, void* stream);
+int rgbac_avgpool2_any(int batch, int channels, int hc, int wc, int hc_out, int wc_out,
+                       const rgbac_ssim_any_desc* descs, const float* x, const float* y,
+                       const float* mask, float* x_out, float* y_out, float* mask_out,
+                       void* stream);
+int rgbac_ssim_any_reduce(int levels, int batch, int channels, int win_size, int masked,
+                          const rgbac_ssim_any_desc* descs, const int32_t* plane_h,
+                          const int32_t* plane_w, const int32_t* max_tiles,
+                          const int64_t* partial_offsets, int64_t partial_floats,
+                          const float* partials, float* ssim_out, float* cs_out, void* stream);
+
+/* Per-image rate (csrc/bits_any.hip), evaluation only.  lik: fp32 likelihoods as the GAUSS
+ * epilogues (aux1) and rgbac_eb_forward (lik) store them, laid out [segments][batch]
+ * [n_per_image] (the slices of one model side by side; segments = 1 for one tensor).
+ * bits[b] = sum over segments, then elements, of (double) clamp(-logf(lik + 1e-10f) / ln 2, 0,
+ * 50) -- the forward's own fp32 bits term -- through fixed-order block partials: DEVICE fp64
+ * bits[batch]; scratch: batch * rgbac_image_bits_blocks(n_per_image, segments) doubles, no
+ * initial contents needed.  No atomics: bit-reproducible, image by image. */
+int rgbac_image_bits_blocks(int64_t n_per_image, int segments);
+int rgbac_image_bits(int batch, int64_t n_per_image, int segments, const float* lik,
+                     double* scratch, double* bits, void* stream);
+
 /* Data-parallel gradient exchange (csrc/comm.cpp; BASELINE config 5 -- the reference trains
  * on one GPU, DataParallel is commented out at trainRGB.py:374, so no reference interface is
  * replaced: this is the all-reduce of rgbac/parallel.py's gradient buckets).  RCCL is called
