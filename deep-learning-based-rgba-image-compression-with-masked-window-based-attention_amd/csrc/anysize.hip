@@ -196,6 +196,139 @@ rgba_unpack_kernel(const ImgDesc* __restrict__ descs, int hp, int wp, long long 
   }
 }
 
+// rgba_opaque_kernel with a second flag: scratch[(b * RGBAC_OPAQUE_BLOCKS + k) * 2 + {0, 1}] =
+// {every alpha byte block k saw is 255, every one is 0} (a block without pixels writes 1, 1; an
+// empty descriptor 0, 0)
+__global__ void __launch_bounds__(256)
+rgba_alpha_class_kernel(const ImgDesc* __restrict__ descs, int32_t* __restrict__ scratch) {
+  const int b = blockIdx.y;
+  const ImgDesc d = descs[b];
+  const bool ok = d.ptr && d.h > 0 && d.w > 0;
+  int full = ok ? 1 : 0, none = ok ? 1 : 0;
+  if (ok) {
+    const long long items = (long long)d.h * d.w;
+    const uint8_t* base = reinterpret_cast<const uint8_t*>(d.ptr);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items;
+         i += (long long)gridDim.x * 256) {
+      const int r = (int)(i / d.w), c = (int)(i - (long long)r * d.w);
+      const uchar4 p =
+          *reinterpret_cast<const uchar4*>(base + (long long)r * d.row_stride_bytes + 4 * (size_t)c);
+      full &= p.w == 255 ? 1 : 0;
+      none &= p.w == 0 ? 1 : 0;
+    }
+  }
+  full = __syncthreads_and(full);
+  none = __syncthreads_and(none);
+  if (threadIdx.x == 0) {
+    int32_t* o = scratch + ((size_t)b * gridDim.x + blockIdx.x) * 2;
+    o[0] = full ? 1 : 0;
+    o[1] = none ? 1 : 0;
+  }
+}
+
+// one thread per rectangle: the ANDs of its block flags -> 1 opaque, 2 transparent, 0 mixed
+__global__ void __launch_bounds__(256)
+rgba_alpha_class_final_kernel(int batch, const int32_t* __restrict__ scratch,
+                              int32_t* __restrict__ cls) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= batch) return;
+  int full = 1, none = 1;
+  for (int k = 0; k < RGBAC_OPAQUE_BLOCKS; ++k) {
+    full &= scratch[((size_t)b * RGBAC_OPAQUE_BLOCKS + k) * 2];
+    none &= scratch[((size_t)b * RGBAC_OPAQUE_BLOCKS + k) * 2 + 1];
+  }
+  cls[b] = full ? 1 : (none ? 2 : 0);
+}
+
+// One fp32 multiply / add, rounded on its own.  The header's __fmul_rn / __fadd_rn are plain
+// operators under the default contraction mode: once inlined, a product feeding a sum becomes one
+// FMA, which rounds once.  The blend's sums of products must match their numpy twin bit for bit
+// (alpha is k/255 and the weights are dyadic, so sums land on the quantiser's ties), hence
+// operators compiled with contraction off.
+__device__ __forceinline__ float mul_rn(float x, float y) {
+#pragma clang fp contract(off)
+  return x * y;
+}
+__device__ __forceinline__ float add_rn(float x, float y) {
+#pragma clang fp contract(off)
+  return x + y;
+}
+
+// Seam blend of decoded tiles (include/rgbac.h has the rule).  One axis of one pixel: the later
+// tile j that holds p, whether the tile before it holds p too, and the weight of each.
+struct BlendAxis {
+  int j;          // last tile whose origin is <= p
+  bool two;       // tile j - 1 covers p as well
+  float w0, w1;   // weights of tile j - 1 (when two) and of tile j
+};
+__device__ __forceinline__ BlendAxis blend_axis(int p, int k, int stride, int overlap) {
+  BlendAxis a;
+  int j = p / stride;
+  a.j = j < k - 1 ? j : k - 1;
+  const int d = p - a.j * stride;
+  a.two = a.j >= 1 && d < overlap;
+  a.w1 = 1.0f;
+  a.w0 = 0.0f;
+  if (a.two) {
+    a.w1 = __fdiv_rn(add_rn((float)d, 0.5f), (float)overlap);
+    a.w0 = add_rn(1.0f, -a.w1);
+  }
+  return a;
+}
+
+// grid (capped, nout): the blocks of output k walk its dst.h x dst.w pixels, one dword per lane,
+// adjacent lanes adjacent pixels of a row (the fp32 planes are read 4 bytes per lane from
+// consecutive addresses: a region may start at any column, so nothing wider is aligned)
+__global__ void __launch_bounds__(256)
+rgba_blend_tiles_kernel(const rgbac_blend_desc* __restrict__ outs, int ntiles,
+                        const rgbac_tile_desc* __restrict__ tiles) {
+  const rgbac_blend_desc o = outs[blockIdx.y];
+  const ImgDesc d = o.dst;
+  // a descriptor that does not hold together writes nothing (the host builds them checked)
+  if (!d.ptr || d.h <= 0 || d.w <= 0 || o.tile <= 0 || o.overlap < 0 ||
+      o.overlap > o.tile / 2 || o.ky <= 0 || o.kx <= 0 || o.y0 < 0 || o.x0 < 0 || o.tile0 < 0 ||
+      (long long)o.ky * o.kx > (long long)ntiles - o.tile0)
+    return;
+  const int stride = o.tile - o.overlap;
+  const long long items = (long long)d.h * d.w;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items;
+       i += (long long)gridDim.x * 256) {
+    const int r = (int)(i / d.w), c = (int)(i - (long long)r * d.w);
+    const int py = o.y0 + r, px = o.x0 + c;
+    const BlendAxis ay = blend_axis(py, o.ky, stride, o.overlap);
+    const BlendAxis ax = blend_axis(px, o.kx, stride, o.overlap);
+    float A = 0.0f, Wp = 0.0f, C[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {                    // row-major over the 2 x 2 candidates
+      const bool hy = s >> 1, hx = s & 1;            // 0: the earlier tile, 1: tile j
+      if ((!hy && !ay.two) || (!hx && !ax.two)) continue;
+      const int ty = hy ? ay.j : ay.j - 1, tx = hx ? ax.j : ax.j - 1;
+      const rgbac_tile_desc t = tiles[o.tile0 + ty * o.kx + tx];
+      const int ly = py - t.oy, lx = px - t.ox;
+      if (!t.x_hat || ly < 0 || lx < 0 || ly >= t.ey || lx >= t.ex || t.ey > t.hp || t.ex > t.wp)
+        continue;
+      const float w = mul_rn(hy ? ay.w1 : ay.w0, hx ? ax.w1 : ax.w0);
+      const size_t plane = (size_t)t.hp * t.wp, at = (size_t)ly * t.wp + lx;
+      const float a = t.alpha ? t.alpha[at] : 1.0f;
+      A = add_rn(A, mul_rn(w, a));
+      if (a > 0.0f) {
+        Wp = add_rn(Wp, w);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+          C[ch] = add_rn(C[ch], mul_rn(w, t.x_hat[ch * plane + at]));
+      }
+    }
+    uchar4 p;
+    p.w = quant_u8(A);
+    const bool zero = p.w == 0 || !(Wp > 0.0f);
+    p.x = zero ? (uint8_t)0 : quant_u8(__fdiv_rn(C[0], Wp));
+    p.y = zero ? (uint8_t)0 : quant_u8(__fdiv_rn(C[1], Wp));
+    p.z = zero ? (uint8_t)0 : quant_u8(__fdiv_rn(C[2], Wp));
+    *reinterpret_cast<uchar4*>(reinterpret_cast<uint8_t*>(d.ptr) +
+                               (long long)r * d.row_stride_bytes + 4 * (size_t)c) = p;
+  }
+}
+
 constexpr int kRegionMaxBlocks = 64;     // per image
 inline int region_blocks(int hp, int wp) {
   long long b = ((long long)hp * (wp >> 2) + kReduceThreads - 1) / kReduceThreads;
@@ -322,6 +455,36 @@ extern "C" int rgbac_rgba_opaque(int batch, const rgbac_image_desc* descs, int32
   hipLaunchKernelGGL(rgba_opaque_final_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch,
                      scratch, flags);
   return check_launch("rgba_opaque_final_kernel");
+}
+
+extern "C" int rgbac_rgba_alpha_class(int batch, const rgbac_image_desc* descs, int32_t* scratch,
+                                      int32_t* cls, void* stream) {
+  RGBAC_REQUIRE(batch > 0 && batch < 65536, "batch");
+  RGBAC_REQUIRE(descs && scratch && cls, "null pointer");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(rgba_alpha_class_kernel, dim3(RGBAC_OPAQUE_BLOCKS, batch), dim3(256), 0, st,
+                     descs, scratch);
+  int rc = check_launch("rgba_alpha_class_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(rgba_alpha_class_final_kernel, dim3((batch + 255) / 256), dim3(256), 0, st,
+                     batch, scratch, cls);
+  return check_launch("rgba_alpha_class_final_kernel");
+}
+
+extern "C" int rgbac_rgba_blend_tiles(int nout, const rgbac_blend_desc* outs, int ntiles,
+                                      const rgbac_tile_desc* tiles, int64_t max_pixels,
+                                      void* stream) {
+  RGBAC_REQUIRE(nout > 0 && nout < 65536, "output count");
+  RGBAC_REQUIRE(ntiles > 0, "tile count");
+  RGBAC_REQUIRE(outs && tiles, "null descriptor pointer");
+  RGBAC_REQUIRE(max_pixels > 0, "max_pixels");
+  // the capped grid is shared among the outputs
+  int gx = any_grid((long long)max_pixels);
+  const int per = (device_cus() * 16 + nout - 1) / nout;
+  if (gx > per) gx = per;
+  hipLaunchKernelGGL(rgba_blend_tiles_kernel, dim3(gx, nout), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), outs, ntiles, tiles);
+  return check_launch("rgba_blend_tiles_kernel");
 }
 
 extern "C" int rgbac_pad_nchw(int batch, int channels, int h, int w, int hp, int wp, int mode,

@@ -93,6 +93,21 @@ class ImageDesc(ctypes.Structure):
                 ("row_stride_bytes", ctypes.c_int64)]
 
 
+class TileDesc(ctypes.Structure):
+    """rgbac_tile_desc"""
+    _fields_ = [("x_hat", ctypes.c_void_p), ("alpha", ctypes.c_void_p),
+                ("hp", ctypes.c_int32), ("wp", ctypes.c_int32),
+                ("oy", ctypes.c_int32), ("ox", ctypes.c_int32),
+                ("ey", ctypes.c_int32), ("ex", ctypes.c_int32)]
+
+
+class BlendDesc(ctypes.Structure):
+    """rgbac_blend_desc"""
+    _fields_ = [("dst", ImageDesc), ("tile0", ctypes.c_int32), ("ky", ctypes.c_int32),
+                ("kx", ctypes.c_int32), ("tile", ctypes.c_int32), ("overlap", ctypes.c_int32),
+                ("y0", ctypes.c_int32), ("x0", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class SsimAnyDesc(ctypes.Structure):
     """rgbac_ssim_any_desc"""
     _fields_ = [("h", ctypes.c_int32), ("w", ctypes.c_int32), ("tiles_x", ctypes.c_int32),
@@ -195,6 +210,8 @@ SIGNATURES = {
     "rgbac_rgba_pack": [_I32, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP],
     "rgbac_rgba_opaque": [_I32, _VP, _VP, _VP, _VP],
     "rgbac_rgba_pack_modes": [_I32, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP],
+    "rgbac_rgba_alpha_class": [_I32, _VP, _VP, _VP, _VP],
+    "rgbac_rgba_blend_tiles": [_I32, _VP, _I32, _VP, _I64, _VP],
     "rgbac_pad_nchw": [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP],
     "rgbac_rgba_unpack": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP],
     "rgbac_region_error_blocks": [_I32, _I32],

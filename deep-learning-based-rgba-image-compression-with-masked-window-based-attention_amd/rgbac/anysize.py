@@ -162,6 +162,31 @@ def _opaque(dev, entries):
     return flags
 
 
+def alpha_class(images, device="cuda"):
+    """-> device int32 (B,): 1 where every alpha byte of the image is 255 (exactly where
+    opaque_flags says 1), 2 where every one is 0, else 0 (rgbac_rgba_alpha_class).  Nothing is
+    read back here."""
+    dev, sizes, entries, keep = _sources(images, device, "alpha_class")
+    return _alpha_class(dev, entries)
+
+
+_MAX_RECTS = 65535            # rectangles per launch (the grid's y dimension)
+
+
+def _alpha_class(dev, entries):
+    parts = []
+    for lo in range(0, len(entries), _MAX_RECTS):
+        part = entries[lo:lo + _MAX_RECTS]
+        B = len(part)
+        descs = _upload_descs(part, dev)
+        scratch = torch.empty(B * _lib.OPAQUE_BLOCKS * 2, dtype=torch.int32, device=dev)
+        cls = torch.empty(B, dtype=torch.int32, device=dev)
+        _lib.call("rgbac_rgba_alpha_class", B, descs.data_ptr(), scratch.data_ptr(),
+                  cls.data_ptr(), _lib.stream_ptr(dev))
+        parts.append(cls)
+    return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+
 def pack_rgba_modes(images, modes, device="cuda"):
     """pack_rgba with one pad mode per image: ``modes`` a device int32 (B,) tensor of
     rgbac_pad_mode values (1 replicates, anything else pads transparent, so opaque_flags'

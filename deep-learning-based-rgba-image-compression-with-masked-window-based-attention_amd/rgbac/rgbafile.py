@@ -205,8 +205,6 @@ def encode_rgba(masknet, net, images, chunk=256, debug=None):
     sizes) -> list[bytes], one complete file per image.  ``chunk``: symbols per rANS chunk (see
     AutoEncoder.compress).  ``debug``: a list that receives, per image, the encoder's symbols
     and y_hat ({"alpha": {...} or None, "rgb": {"z", "y", "YH"}})."""
-    from .models._codec import latent_code
-    from .models.AutoEncoderMask_Journal import _run_seq
     dev = _models(masknet, net)
     chunk = int(chunk)
     if chunk <= 0 or chunk >= 1 << 31:
@@ -222,31 +220,51 @@ def encode_rgba(masknet, net, images, chunk=256, debug=None):
     if debug is not None:
         debug[:] = [None] * len(sizes)
     for members in groups.values():
-        sel = torch.tensor(members, device=dev)
-        p = anysize._pack(dev, [sizes[k] for k in members], [entries[k] for k in members], None,
-                          flags_dev[sel].contiguous())
-        nonop = [j for j, k in enumerate(members) if not flags[k]]
-        jobs = []
-        with rt.fixed_tiles(per_image=True):
-            if nonop:
-                am = p["alpha"][torch.tensor(nonop, device=dev)]
-                ya = _run_seq(masknet.EncoderMask, rt.to_nhwc(am, masknet.compute_dtype))
-                lat_a = latent_code(masknet, y=ya)
-                jobs += _latent_jobs(masknet, *lat_a[1:])
-            _, me = mask_pyramid(p["alpha"], 4)          # the TRUE alpha, as compress takes it
-            y = net.Encoder.nhwc(rt.to_nhwc(p["masked"], net.compute_dtype), me[1], me[2])
-            lat_r = latent_code(net, y=y)
-            jobs += _latent_jobs(net, *lat_r[1:])
-        blobs = encode_image_major(jobs, chunk)
-        for j, k in enumerate(members):
-            a = nonop.index(j) if j in nonop else None
-            secs = ([b"", b""] if a is None else [blobs[0][a], blobs[1][a]]) + \
-                [blobs[-2][j], blobs[-1][j]]
-            files[k] = build_rgba_file(*sizes[k], chunk, a is None, info_a, info_r, secs)
+        coded = _encode_group(masknet, net, dev, [sizes[k] for k in members],
+                              [entries[k] for k in members], [flags[k] for k in members],
+                              flags_dev[torch.tensor(members, device=dev)].contiguous(), chunk,
+                              debug is not None)
+        for k, (secs, dbg) in zip(members, coded):
+            files[k] = build_rgba_file(*sizes[k], chunk, bool(flags[k]), info_a, info_r, secs)
             if debug is not None:
-                debug[k] = {"alpha": None if a is None else _per_image(*lat_a, a),
-                            "rgb": _per_image(*lat_r, j)}
+                debug[k] = dbg
     return files
+
+
+def _encode_group(masknet, net, dev, sizes, entries, opaque, opaque_dev, chunk, want_debug):
+    """One batched coding pass over images that share a canvas (encode_rgba's group body; the
+    tiled encoder runs its tiles through it too).  sizes / entries: as anysize._sources returns
+    them; opaque: per image, truthy where every alpha byte is 255 (host list), opaque_dev the
+    same as a device int32 tensor (the pack's per-image pad modes).  -> per image
+    (its four sections in SECTIONS order, the alpha ones b"" when opaque; its debug record or
+    None)."""
+    from .models._codec import latent_code
+    from .models.AutoEncoderMask_Journal import _run_seq
+    p = anysize._pack(dev, sizes, entries, None, opaque_dev)
+    nonop = [j for j, f in enumerate(opaque) if not f]
+    jobs = []
+    with rt.fixed_tiles(per_image=True):
+        if nonop:
+            am = p["alpha"][torch.tensor(nonop, device=dev)]
+            ya = _run_seq(masknet.EncoderMask, rt.to_nhwc(am, masknet.compute_dtype))
+            lat_a = latent_code(masknet, y=ya)
+            jobs += _latent_jobs(masknet, *lat_a[1:])
+        _, me = mask_pyramid(p["alpha"], 4)          # the TRUE alpha, as compress takes it
+        y = net.Encoder.nhwc(rt.to_nhwc(p["masked"], net.compute_dtype), me[1], me[2])
+        lat_r = latent_code(net, y=y)
+        jobs += _latent_jobs(net, *lat_r[1:])
+    blobs = encode_image_major(jobs, chunk)
+    out = []
+    for j in range(len(sizes)):
+        a = nonop.index(j) if j in nonop else None
+        secs = ([b"", b""] if a is None else [blobs[0][a], blobs[1][a]]) + \
+            [blobs[-2][j], blobs[-1][j]]
+        dbg = None
+        if want_debug:
+            dbg = {"alpha": None if a is None else _per_image(*lat_a, a),
+                   "rgb": _per_image(*lat_r, j)}
+        out.append((secs, dbg))
+    return out
 
 
 @torch.no_grad()
@@ -257,7 +275,6 @@ def decode_rgba(masknet, net, blobs, debug=None):
     one error word of all rANS launches is read once, after the last synthesis is queued.
     ``debug``: a list that receives, per file, the decoded symbols, y_hat and the reconstructed
     alpha plane ({"alpha": {...} or None, "rgb": {...}, "alpha_plane": (hp, wp) fp32})."""
-    from .models._codec import mask_synthesis
     dev = _models(masknet, net)
     blobs = list(blobs)
     if not blobs:
@@ -273,26 +290,42 @@ def decode_rgba(masknet, net, blobs, debug=None):
         debug[:] = [None] * len(blobs)
     for (hp, wp, _), members in groups.items():
         fs = [parsed[k] for k in members]
-        nonop = [j for j, f in enumerate(fs) if not f["opaque"]]
-        with rt.fixed_tiles(per_image=True):
-            alpha = torch.ones((len(fs), 1, hp, wp), device=dev)
-            if nonop:
-                lat_a = _decode_latents(masknet, [fs[j]["alpha_z"] for j in nonop],
-                                        [fs[j]["alpha_y"] for j in nonop], hp, wp, dev, err)
-                xa = mask_synthesis(masknet, lat_a[0])
-                ra = recon_alpha(xa)
-                alpha.index_copy_(0, torch.tensor(nonop, device=dev), ra)
-            lat_r = _decode_latents(net, [f["rgb_z"] for f in fs], [f["rgb_y"] for f in fs],
-                                    hp, wp, dev, err)
-            _, md = mask_pyramid(alpha, 4)
-            x_hat = rt.to_nchw(net.Decoder.nhwc(lat_r[0], md[1], md[2])).clamp_(0, 1)
+        x_hat, alpha, dbgs = _decode_group(masknet, net, fs, hp, wp, dev, err, debug is not None)
         rgba = anysize.unpack_rgba(x_hat, alpha, [(f["h"], f["w"]) for f in fs])
         for j, k in enumerate(members):
             outs[k] = rgba[j]
             if debug is not None:
-                a = nonop.index(j) if j in nonop else None
-                debug[k] = {"alpha": None if a is None else _per_image(*lat_a, a),
-                            "rgb": _per_image(*lat_r, j), "alpha_plane": alpha[j, 0].clone(),
-                            "alpha_x_hat": None if a is None else xa[a, 0].clone()}
+                debug[k] = dbgs[j]
     _raise_code("RGBA file decode", int(err.item()))
     return outs
+
+
+def _decode_group(masknet, net, fs, hp, wp, dev, err, want_debug):
+    """One batched decoding pass over parsed files that share the canvas hp x wp and a chunk size
+    (decode_rgba's group body; the tiled decoder runs its tiles through it too).  fs: dicts with
+    "opaque" and the four SECTIONS layouts.  -> (x_hat (B,3,hp,wp) fp32 clamped to [0, 1], the
+    reconstructed alpha (B,1,hp,wp) fp32, ones for an opaque member, the per-member debug
+    records or None).  Nothing is read back; rANS errors land in ``err``."""
+    from .models._codec import mask_synthesis
+    nonop = [j for j, f in enumerate(fs) if not f["opaque"]]
+    with rt.fixed_tiles(per_image=True):
+        alpha = torch.ones((len(fs), 1, hp, wp), device=dev)
+        if nonop:
+            lat_a = _decode_latents(masknet, [fs[j]["alpha_z"] for j in nonop],
+                                    [fs[j]["alpha_y"] for j in nonop], hp, wp, dev, err)
+            xa = mask_synthesis(masknet, lat_a[0])
+            ra = recon_alpha(xa)
+            alpha.index_copy_(0, torch.tensor(nonop, device=dev), ra)
+        lat_r = _decode_latents(net, [f["rgb_z"] for f in fs], [f["rgb_y"] for f in fs],
+                                hp, wp, dev, err)
+        _, md = mask_pyramid(alpha, 4)
+        x_hat = rt.to_nchw(net.Decoder.nhwc(lat_r[0], md[1], md[2])).clamp_(0, 1)
+    dbgs = None
+    if want_debug:
+        dbgs = []
+        for j in range(len(fs)):
+            a = nonop.index(j) if j in nonop else None
+            dbgs.append({"alpha": None if a is None else _per_image(*lat_a, a),
+                         "rgb": _per_image(*lat_r, j), "alpha_plane": alpha[j, 0].clone(),
+                         "alpha_x_hat": None if a is None else xa[a, 0].clone()})
+    return x_hat, alpha, dbgs

@@ -715,6 +715,51 @@ int rgbac_rgba_pack_modes(int batch, const rgbac_image_desc* descs, int hp, int 
 int rgbac_rgba_unpack(int batch, const rgbac_image_desc* descs, int hp, int wp,
                       const float* x_hat, const float* alpha, int zero_transparent,
                       void* stream);
+/* Tiled RGBA files (rgbac/rgbatile.py): an image coded as a grid of overlapping tiles, every tile
+ * an image of its own.  Per axis of length n: stride S = tile - overlap, tile i starts at
+ * o_i = i S and spans e_i = min(tile, n - o_i) pixels; 0 <= overlap <= tile / 2, so a pixel lies
+ * in one or two tiles per axis.
+ * rgbac_rgba_alpha_class: cls[b] = 1 if every alpha byte inside rectangle b is 255, 2 if every
+ *   one is 0, else 0 (0 for an empty descriptor), for the ragged batch as rgbac_rgba_opaque
+ *   takes it; cls[b] == 1 exactly where rgbac_rgba_opaque's flag is 1.  DEVICE int32 cls[batch];
+ *   scratch: DEVICE int32[batch * RGBAC_OPAQUE_BLOCKS * 2], no initial contents needed.  Integer
+ *   AND only: bit-reproducible.
+ * rgbac_rgba_blend_tiles: decoded tiles -> uint8 RGBA, `nout` output rectangles in one launch.
+ *   tiles: DEVICE array of `ntiles` rgbac_tile_desc; outs: DEVICE array of `nout`
+ *   rgbac_blend_desc, output k using tiles[tile0 .. tile0 + ky kx) in row-major grid order and
+ *   writing image rows y0 .. y0 + dst.h, columns x0 .. x0 + dst.w to dst (bytes outside stay
+ *   untouched).  max_pixels: the largest dst.h * dst.w (sizes the grid only).
+ *   Per axis a pixel p lies in tile j = min(p / S, k - 1) and, when j >= 1 and p - o_j < overlap,
+ *   in tile j - 1 too: then tile j weighs r = (float(p - o_j) + 0.5f) / float(overlap) and tile
+ *   j - 1 weighs 1.0f - r; a pixel in one tile weighs exactly 1.0f.  Per pixel, over its up to
+ *   four tiles in row-major order with w_t = wy wx and a_t the tile's alpha (1.0f where its
+ *   alpha pointer is NULL; a tile whose x_hat is NULL is skipped: alpha 0, no colour):
+ *     A = sum w_t a_t,  W+ = sum of w_t over a_t > 0,  C_c = (sum over a_t > 0 of w_t x_t,c) / W+
+ *   (0 when no tile has a_t > 0), every multiply, add and divide rounded in fp32 on its own (no
+ *   FMA), the sums starting from 0.0f; then u8 = (uint8) clamp(v*255 + 0.5, 0, 255) for A and
+ *   each C_c as rgbac_rgba_unpack does, and R = G = B = 0 where the alpha byte is 0.  A pixel in
+ *   one tile gets the bytes rgbac_rgba_unpack (zero_transparent = 1) writes for that tile.
+ *   Nothing outside a tile's ey x ex rectangle is read; a descriptor that does not hold together
+ *   (tile, overlap, grid, tile range, extents against the planes) writes nothing. */
+typedef struct rgbac_tile_desc {
+  const float* x_hat;        /* 3 fp32 planes of hp x wp, contiguous; NULL: transparent / absent */
+  const float* alpha;        /* 1 fp32 plane of hp x wp; NULL: 1.0 everywhere (an opaque tile) */
+  int32_t hp, wp;            /* plane size (the tile's canvas) */
+  int32_t oy, ox;            /* origin in the image */
+  int32_t ey, ex;            /* extent: the rectangle of the planes that belongs to the image */
+} rgbac_tile_desc;
+typedef struct rgbac_blend_desc {
+  rgbac_image_desc dst;      /* the (hr, wr, 4) uint8 output */
+  int32_t tile0;             /* this image's first entry of the tile table */
+  int32_t ky, kx;            /* its grid */
+  int32_t tile, overlap;
+  int32_t y0, x0;            /* where dst's first pixel lies in the image */
+  int32_t reserved;          /* 0 */
+} rgbac_blend_desc;
+int rgbac_rgba_alpha_class(int batch, const rgbac_image_desc* descs, int32_t* scratch,
+                           int32_t* cls, void* stream);
+int rgbac_rgba_blend_tiles(int nout, const rgbac_blend_desc* outs, int ntiles,
+                           const rgbac_tile_desc* tiles, int64_t max_pixels, void* stream);
 int rgbac_region_error_blocks(int hp, int wp);
 int rgbac_region_error(int batch, int channels, const rgbac_image_desc* descs, int hp, int wp,
                        const float* x, const float* y, const float* mask, double* scratch,
