@@ -116,6 +116,8 @@ class SsimAnyDesc(ctypes.Structure):
 
 PAD_MODES = dict(transparent=0, replicate=1)   # enum rgbac_pad_mode
 OPAQUE_BLOCKS = 32                              # RGBAC_OPAQUE_BLOCKS
+# RGBAC_ALPHA_BLOCK, _GROUP, _CONTEXTS, _HIST_BLOCKS, _TABLE_U16
+ALPHA_BLOCK, ALPHA_GROUP, ALPHA_CONTEXTS, ALPHA_HIST_BLOCKS, ALPHA_TABLE_U16 = 16, 64, 5, 16, 1288
 
 _VP, _I32, _I64, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 _D = ctypes.c_double
@@ -272,6 +274,14 @@ SIGNATURES = {
     "rgbac_rans_chunk_decode_host": [_VP, _I64, _VP, _VP, _VP, _I64, _I64, _VP, _VP, _I64, _I32,
                                      _VP, _I32, _VP, _VP, _I32, _VP,
                                      ctypes.POINTER(ctypes.c_int32)],
+    # lossless alpha planes (csrc/alpha_exact.hip)
+    "rgbac_alpha_exact_classify": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP],
+    "rgbac_alpha_exact_tables": [_I32, _VP, _I32, _VP, _I32, _VP, _VP, _VP, _VP, _VP],
+    "rgbac_alpha_exact_sizes": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP],
+    "rgbac_alpha_exact_encode": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP,
+                                 _I64, _VP, _VP],
+    "rgbac_alpha_exact_decode": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP,
+                                 _I64, _VP, _VP],
 }
 _RESTYPE = {"rgbac_last_error": ctypes.c_char_p, "rgbac_rans_encoder_bound": ctypes.c_int64,
             "rgbac_winattn_block_workspace": ctypes.c_int64,

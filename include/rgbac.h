@@ -999,6 +999,73 @@ int rgbac_rans_chunk_decode_host(const uint32_t* payload, int64_t payload_words,
                                  const int32_t* cdf_sizes, const int32_t* offsets, int ncdf,
                                  int32_t* out, int32_t* err);
 
+/* Lossless alpha planes (csrc/alpha_exact.hip, rgbac/alphaexact.py): a
+ * static-model, context-conditioned predictive rANS coder for uint8 planes, on the device for a
+ * whole ragged batch.  A plane is cut into RGBAC_ALPHA_BLOCK-square blocks, row-major (edge
+ * blocks smaller); a block of equal bytes is constant (class word 1 | value << 8), any other is
+ * coded (class word 0) as one chunk of the chunked rANS format above.  The model (MED
+ * prediction inside the block, five contexts, symbol = (a - pred) & 255) and the rule that
+ * turns counts into 16-bit frequencies are fixed by the format: see csrc/alpha_exact.hip.
+ *   descs: DEVICE array of `batch` rgbac_image_desc with ptr = the plane's first byte (no
+ *     alignment asked), h, w, row_stride_bytes; pixel_stride = bytes between the pixels of a
+ *     row, 1 (a plain plane) or 4 (ptr at the alpha byte of packed RGBA: coded in place).
+ *   block_base: DEVICE int32[batch], image b's first entry of the per-block arrays (cls, counts,
+ *     ends, word_off: `total_blocks` entries each, an image's blocks row-major and contiguous).
+ *   groups: DEVICE array of `ngroups` rgbac_alpha_group; a group is up to RGBAC_ALPHA_GROUP
+ *     consecutive blocks of one image starting at block0, served by one workgroup; every block of
+ *     every image must lie in exactly one group.
+ *   tables: DEVICE uint16[batch * RGBAC_ALPHA_TABLE_U16], 4-byte aligned; per image 5 x 256
+ *     exclusive sums of the frequencies (mod 2^16), then per context the last symbol that has a
+ *     frequency as int16 (-1: the context is empty), then 3 zeros.
+ * A descriptor, group or block range that does not hold together is skipped (kErrChunk in the
+ * error word where there is one); no kernel reads or writes outside its planes and arrays.
+ * rgbac_alpha_exact_classify: cls for every block of every image, one launch.
+ * rgbac_alpha_exact_tables: two launches.  Histograms of the coded blocks' symbols per image
+ *   and context (integer LDS atomics, per-workgroup partials: DEVICE uint32[batch *
+ *   RGBAC_ALPHA_HIST_BLOCKS * 1280], no initial contents needed, summed in index order), then
+ *   freqs: DEVICE int32[batch * 1280] (sum 2^16 per non-empty context, all 0 for an empty one)
+ *   and `tables`.
+ * rgbac_alpha_exact_sizes: counts[k] = the words of block k's chunk, 0 for a constant block.
+ * rgbac_alpha_exact_encode: after the caller's inclusive scan of counts into ends, stores block
+ *   k's words at payload[ends[k] - counts[k], ends[k]).
+ * rgbac_alpha_exact_decode: one launch; block k's words are payload[word_off[k], + counts[k]);
+ *   every read is bounded by them, and a chunk that does not end with every word read and the
+ *   coder's state back at its start value is reported as corrupt (error codes as for
+ *   rgbac_rans_chunk_decode; a bad chunk's block is written as zeros).  err: DEVICE int32,
+ *   zeroed by the caller, first non-zero code wins. */
+#define RGBAC_ALPHA_BLOCK 16
+#define RGBAC_ALPHA_GROUP 64
+#define RGBAC_ALPHA_CONTEXTS 5
+#define RGBAC_ALPHA_HIST_BLOCKS 16
+#define RGBAC_ALPHA_TABLE_U16 1288
+typedef struct rgbac_alpha_group {
+  int32_t image;             /* index into descs */
+  int32_t block0;            /* the group's first block of that image */
+} rgbac_alpha_group;
+int rgbac_alpha_exact_classify(int batch, const rgbac_image_desc* descs, int pixel_stride,
+                               int ngroups, const rgbac_alpha_group* groups,
+                               const int32_t* block_base, int total_blocks, int32_t* cls,
+                               void* stream);
+int rgbac_alpha_exact_tables(int batch, const rgbac_image_desc* descs, int pixel_stride,
+                             const int32_t* block_base, int total_blocks, const int32_t* cls,
+                             uint32_t* partials, int32_t* freqs, uint16_t* tables, void* stream);
+int rgbac_alpha_exact_sizes(int batch, const rgbac_image_desc* descs, int pixel_stride,
+                            int ngroups, const rgbac_alpha_group* groups,
+                            const int32_t* block_base, int total_blocks, const int32_t* cls,
+                            const uint16_t* tables, int32_t* counts, int32_t* err, void* stream);
+int rgbac_alpha_exact_encode(int batch, const rgbac_image_desc* descs, int pixel_stride,
+                             int ngroups, const rgbac_alpha_group* groups,
+                             const int32_t* block_base, int total_blocks, const int32_t* cls,
+                             const uint16_t* tables, const int32_t* counts, const int64_t* ends,
+                             uint32_t* payload, int64_t payload_words, int32_t* err,
+                             void* stream);
+int rgbac_alpha_exact_decode(int batch, const rgbac_image_desc* descs, int pixel_stride,
+                             int ngroups, const rgbac_alpha_group* groups,
+                             const int32_t* block_base, int total_blocks, const int32_t* cls,
+                             const uint16_t* tables, const int64_t* word_off,
+                             const int32_t* counts, const uint32_t* payload,
+                             int64_t payload_words, int32_t* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
