@@ -274,6 +274,20 @@ SIGNATURES = {
     "rgbac_rans_chunk_decode_host": [_VP, _I64, _VP, _VP, _VP, _I64, _I64, _VP, _VP, _I64, _I32,
                                      _VP, _I32, _VP, _VP, _I32, _VP,
                                      ctypes.POINTER(ctypes.c_int32)],
+    # lane-interleaved rANS coder (csrc/rans_lanes.hip)
+    "rgbac_rans_lanes_sizes": [_VP, _VP, _I64, _I64, _VP, _VP, _I64, _I32, _I32, _VP, _I32, _VP,
+                               _VP, _I32, _VP, _VP, _VP],
+    "rgbac_rans_lanes_encode": [_VP, _VP, _I64, _I64, _VP, _VP, _I64, _I32, _I32, _VP, _I32, _VP,
+                                _VP, _I32, _VP, _VP, _VP, _I64, _VP, _VP],
+    "rgbac_rans_lanes_decode": [_VP, _I64, _VP, _VP, _VP, _I64, _I64, _VP, _VP, _I64, _I32, _I32,
+                                _VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP],
+    "rgbac_rans_lanes_encode_host": [_VP, _VP, _I64, _I64, _VP, _VP, _I64, _I32, _I32, _VP, _I32,
+                                     _VP, _VP, _I32, _VP, _VP, _I64,
+                                     ctypes.POINTER(ctypes.c_int64),
+                                     ctypes.POINTER(ctypes.c_int32)],
+    "rgbac_rans_lanes_decode_host": [_VP, _I64, _VP, _VP, _VP, _I64, _I64, _VP, _VP, _I64, _I32,
+                                     _I32, _VP, _I32, _VP, _VP, _I32, _VP,
+                                     ctypes.POINTER(ctypes.c_int32)],
     # lossless alpha planes (csrc/alpha_exact.hip)
     "rgbac_alpha_exact_classify": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP],
     "rgbac_alpha_exact_tables": [_I32, _VP, _I32, _VP, _I32, _VP, _VP, _VP, _VP, _VP],

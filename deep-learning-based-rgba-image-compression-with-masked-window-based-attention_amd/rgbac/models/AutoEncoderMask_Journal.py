@@ -6,6 +6,7 @@ import torch
 import torch.nn as nn
 
 from .. import runtime as rt
+from ..ans import LANES_DEFAULT
 from ..entropy import EntropyBottleneck, GaussianConditional
 from ..layers.GDN import GDN
 from ..layers.Masked_Attention import _fused_ok, run_bottlenecks_fused
@@ -175,11 +176,12 @@ class AutoEncoder(_CompressionModelMixin, nn.Module):
         """The latent width under the RGB model's name (the shared latent_code reads it)."""
         return self.maskM
 
-    def compress(self, mask, *, coder="host", chunk=256):
+    def compress(self, mask, *, coder="host", chunk=256, lanes=LANES_DEFAULT[0],
+                 steps=LANES_DEFAULT[1]):
         """The alpha plane's bitstream (rgbac/models/_codec.py): the RGB model's compress over
         EncoderMask; the same dict and stream formats."""
         from ._codec import compress_mask
-        return compress_mask(self, mask, coder=coder, chunk=chunk)
+        return compress_mask(self, mask, coder=coder, chunk=chunk, lanes=lanes, steps=steps)
 
     def decompress(self, strings, shape, *, coder="host"):
         """-> {"x_hat": (B,1,H,W) clamped to [0, 1]}, B = len(strings[1]), on the model's

@@ -21,6 +21,7 @@ import torch.nn.functional as F
 
 from .. import _lib
 from .. import runtime as rt
+from ..ans import LANES_DEFAULT
 from ..entropy import EntropyBottleneck, GaussianConditional
 from ..layers.SupplyMask import SupplyMaskToTransform, mask_pyramid
 from ..layers.TransformRGB import Analysis_transform, Synthesis_transform
@@ -186,7 +187,8 @@ class AutoEncoder(_CompressionModelMixin, nn.Module):
         self.gaussian_conditional = GaussianConditional(None)
         self.compute_dtype = torch.float32
 
-    def compress(self, input, mask, *, coder="host", chunk=256):
+    def compress(self, input, mask, *, coder="host", chunk=256, lanes=LANES_DEFAULT[0],
+                 steps=LANES_DEFAULT[1]):
         """:312-371 on the HIP path (rgbac/models/_codec.py) + the host rANS coder.
         coder="device" writes the chunked stream format instead and codes it on the GPU
         (chunks of ``chunk`` symbols; rgbac/ans.py); the result then holds "coder": "device".
@@ -195,7 +197,7 @@ class AutoEncoder(_CompressionModelMixin, nn.Module):
         configurations at ~0.4 bit per latent symbol; a larger chunk cuts
         that cost in proportion and is slower."""
         from ._codec import compress
-        return compress(self, input, mask, coder=coder, chunk=chunk)
+        return compress(self, input, mask, coder=coder, chunk=chunk, lanes=lanes, steps=steps)
 
     def decompress(self, strings, shape, mask, *, coder="host"):
         """:373-416; decodes the batch of len(strings[1]) images (the reference: 1).  Pass the

@@ -29,7 +29,8 @@ import torch
 
 from .. import _lib
 from .. import runtime as rt
-from ..ans import BufferedRansEncoder, ChunkedDecoder, RansDecoder, encode_chunked_many
+from ..ans import (LANES_DEFAULT, BufferedRansEncoder, ChunkedDecoder, LanesDecoder, RansDecoder,
+                   encode_chunked_many, encode_lanes_many)
 from ..layers.SupplyMask import mask_pyramid
 from ..layers.TransformRGB import prep_conv
 from ._latent import _hyper_a, _hyper_s_pair, _musigma_pack
@@ -146,19 +147,22 @@ def _check(model, *ts):
 
 
 def _coder(coder):
-    if coder not in ("host", "device"):
-        raise ValueError(f"coder must be 'host' or 'device', got {coder!r}")
-    return coder == "device"
+    """-> False for the host coder, else the device format's name ("device" or "lanes")."""
+    if coder not in ("host", "device", "lanes"):
+        raise ValueError(f"coder must be 'host', 'device' or 'lanes', got {coder!r}")
+    return coder != "host" and coder
 
 
 def _z_indexes(C, hw, device=None):
     return torch.arange(C, dtype=torch.int32, device=device).view(C, 1).expand(C, hw).reshape(-1)
 
 
-def compress(model, input, mask, coder="host", chunk=256):
+def compress(model, input, mask, coder="host", chunk=256, lanes=LANES_DEFAULT[0],
+             steps=LANES_DEFAULT[1]):
     """:312-371 -> {"strings": [[y_string], z_strings], "shape": z spatial size}; with
     coder="device" the strings are chunked containers (chunks of ``chunk`` symbols) and the
-    dict also holds "coder": "device"."""
+    dict also holds "coder": "device"; with coder="lanes" they are lanes containers (``lanes``
+    lanes of ``steps`` steps per group, rgbac/ans.py) and the dict holds "coder": "lanes"."""
     device_coder = _coder(coder)
     _check(model, input, mask)
     B, _, H, W = input.shape
@@ -169,14 +173,15 @@ def compress(model, input, mask, coder="host", chunk=256):
         _, me = mask_pyramid(mask, 4)                            # EncMakeMask(mask) (:314)
         y = model.Encoder.nhwc(xf, me[1], me[2])                 # :315
         _, z_sym, y_sym, y_idx = latent_code(model, y=y)
-    return _entropy_code(model, z_sym, y_sym, y_idx, device_coder, chunk)
+    return _entropy_code(model, z_sym, y_sym, y_idx, device_coder, chunk, lanes, steps)
 
 
-def _entropy_code(model, z_sym, y_sym, y_idx, device_coder, chunk):
+def _entropy_code(model, z_sym, y_sym, y_idx, device_coder, chunk, lanes=LANES_DEFAULT[0],
+                  steps=LANES_DEFAULT[1]):
     """The symbols of one batch -> compress's dict (either coder); shared by both models."""
     B = z_sym.shape[0]
     if device_coder:
-        return _compress_device(model, z_sym, y_sym, y_idx, chunk)
+        return _compress_device(model, z_sym, y_sym, y_idx, chunk, device_coder, lanes, steps)
     z_host, ys_host, yi_host = z_sym.cpu(), y_sym.cpu(), y_idx.cpu()       # one sync
     eb = model.entropy_bottleneck
     C, zh, zw = z_host.shape[1:]
@@ -193,9 +198,11 @@ def _entropy_code(model, z_sym, y_sym, y_idx, device_coder, chunk):
     return {"strings": [[enc.flush()], z_strings], "shape": torch.Size((zh, zw))}
 
 
-def _compress_device(model, z_sym, y_sym, y_idx, chunk):
-    """The chunked containers of one batch: the y container (one segment per slice) and one z
-    container per image, all coded on the device and brought back with one copy."""
+def _compress_device(model, z_sym, y_sym, y_idx, chunk, coder="device", lanes=LANES_DEFAULT[0],
+                     steps=LANES_DEFAULT[1]):
+    """The chunked (or, coder="lanes", lanes) containers of one batch: the y container (one
+    segment per slice) and one z container per image, all coded on the device and brought back
+    with one copy."""
     eb, gc = model.entropy_bottleneck, model.gaussian_conditional
     dev = z_sym.device
     B, C, zh, zw = z_sym.shape
@@ -204,12 +211,13 @@ def _compress_device(model, z_sym, y_sym, y_idx, chunk):
     ns, n = y_sym.shape
     jobs = [(y_sym, y_idx, y_tab, [n] * ns)]
     jobs += [(z_sym[b], z_idx, z_tab, [C * zh * zw]) for b in range(B)]
-    blobs = encode_chunked_many(jobs, chunk)
+    blobs = (encode_lanes_many(jobs, lanes, steps) if coder == "lanes"
+             else encode_chunked_many(jobs, chunk))
     return {"strings": [[blobs[0]], blobs[1:]], "shape": torch.Size((zh, zw)),
-            "coder": "device"}
+            "coder": coder}
 
 
-def _latent_device(model, strings, zh, zw, dev):
+def _latent_device(model, strings, zh, zw, dev, coder="device"):
     """The device coder's half of decompress: -> (YH, the y decoder whose check() reads the
     shared error word once the synthesis is queued)."""
     eb, gc = model.entropy_bottleneck, model.gaussian_conditional
@@ -218,8 +226,9 @@ def _latent_device(model, strings, zh, zw, dev):
         raise RuntimeError("decompress: strings[0] must hold one y container")
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     # every header is validated (RuntimeError) and every byte uploaded before the first launch
-    z_decs = [ChunkedDecoder(s, dev, err=err) for s in strings[1]]
-    y_dec = ChunkedDecoder(strings[0][0], dev, err=err)
+    Decoder = LanesDecoder if coder == "lanes" else ChunkedDecoder
+    z_decs = [Decoder(s, dev, err=err) for s in strings[1]]
+    y_dec = Decoder(strings[0][0], dev, err=err)
     if len(y_dec.seg_lengths) != model.num_slices:
         raise RuntimeError(f"decompress: the y container has {len(y_dec.seg_lengths)} segments, "
                            f"the model {model.num_slices} slices")
@@ -252,8 +261,8 @@ def _latent_host(model, strings, zh, zw, dev):
     return YH
 
 
-def _decompress_device(model, strings, zh, zw, mask):
-    YH, y_dec = _latent_device(model, strings, zh, zw, mask.device)
+def _decompress_device(model, strings, zh, zw, mask, coder="device"):
+    YH, y_dec = _latent_device(model, strings, zh, zw, mask.device, coder)
     with torch.no_grad():
         _, md = mask_pyramid(mask, 4)
         xh = model.Decoder.nhwc(YH, md[1], md[2])
@@ -269,7 +278,8 @@ def decompress(model, strings, shape, mask, coder="host"):
     device_coder = _coder(coder)
     _check(model, mask)
     if device_coder:
-        return _decompress_device(model, strings, int(shape[0]), int(shape[1]), mask)
+        return _decompress_device(model, strings, int(shape[0]), int(shape[1]), mask,
+                                  device_coder)
     YH = _latent_host(model, strings, int(shape[0]), int(shape[1]), mask.device)
     with torch.no_grad():
         _, md = mask_pyramid(mask, 4)                            # DecMakeMask(mask) (:412)
@@ -278,7 +288,8 @@ def decompress(model, strings, shape, mask, coder="host"):
     return {"x_hat": x_hat}
 
 
-def compress_mask(model, mask, coder="host", chunk=256):
+def compress_mask(model, mask, coder="host", chunk=256, lanes=LANES_DEFAULT[0],
+                  steps=LANES_DEFAULT[1]):
     """The alpha codec's compress: mask (B,1,H,W) -> compress's dict, the same stream formats as
     the RGB codec's.  The reference's alpha model has a forward only
     (models/AutoEncoderMask_Journal.py:248-316); this is the RGB model's compress (:312-371) over
@@ -291,7 +302,7 @@ def compress_mask(model, mask, coder="host", chunk=256):
     with torch.no_grad():
         y = _run_seq(model.EncoderMask, rt.to_nhwc(mask.contiguous().float(), model.compute_dtype))
         _, z_sym, y_sym, y_idx = latent_code(model, y=y)
-    return _entropy_code(model, z_sym, y_sym, y_idx, device_coder, chunk)
+    return _entropy_code(model, z_sym, y_sym, y_idx, device_coder, chunk, lanes, steps)
 
 
 def mask_synthesis(model, YH):
@@ -312,7 +323,7 @@ def decompress_mask(model, strings, shape, coder="host"):
     _check(model)
     zh, zw = int(shape[0]), int(shape[1])
     if device_coder:
-        YH, y_dec = _latent_device(model, strings, zh, zw, dev)
+        YH, y_dec = _latent_device(model, strings, zh, zw, dev, device_coder)
         x_hat = mask_synthesis(model, YH)
         y_dec.check()
     else:

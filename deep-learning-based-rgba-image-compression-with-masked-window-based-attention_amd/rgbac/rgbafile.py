@@ -31,13 +31,16 @@ import torch
 
 from . import anysize
 from . import runtime as rt
-from .ans import ChunkedLayout, MergedChunkedDecoder, _raise_code, encode_image_major
+from .ans import (LANES_DEFAULT, ChunkedLayout, LanesLayout, MergedChunkedDecoder,
+                  MergedLanesDecoder, _check_lanes, _raise_code, encode_image_major,
+                  encode_lanes_image_major)
 from .layers.SupplyMask import mask_pyramid
 from .rgba import recon_alpha
 
 MAGIC = b"RGAF"
 VERSION = 1
-FLAG_OPAQUE, FLAG_ALPHA_BF16, FLAG_RGB_BF16 = 1, 2, 4
+VERSION_LANES = 2                    # the sections are lanes containers; flag bit 3 is set and
+FLAG_OPAQUE, FLAG_ALPHA_BF16, FLAG_RGB_BF16, FLAG_LANES = 1, 2, 4, 8   # chunk holds W | K << 8
 _HEADER = struct.Struct("<4sHHIIIII4I")
 HEADER_BYTES = _HEADER.size          # 44
 SECTIONS = ("alpha_z", "alpha_y", "rgb_z", "rgb_y")
@@ -71,15 +74,20 @@ def _segments(info, hp, wp):
             [info.slice_channels * (8 * zh) * (8 * zw)] * info.num_slices)
 
 
-def build_rgba_file(h, w, chunk, opaque, alpha, rgb, sections):
+def build_rgba_file(h, w, chunk, opaque, alpha, rgb, sections, coder="device"):
     """Header + sections -> bytes.  alpha / rgb: CodecInfo; sections: the four containers'
-    bytes in SECTIONS order (the alpha ones empty when opaque)."""
+    bytes in SECTIONS order (the alpha ones empty when opaque).  coder="lanes": a version-2
+    file of lanes containers, ``chunk`` = (lanes, steps)."""
     flags = ((FLAG_OPAQUE if opaque else 0) | (FLAG_ALPHA_BF16 if alpha.bf16 else 0) |
              (FLAG_RGB_BF16 if rgb.bf16 else 0))
+    version = VERSION
+    if coder == "lanes":
+        lanes, steps = _check_lanes(*chunk)
+        version, flags, chunk = VERSION_LANES, flags | FLAG_LANES, lanes | steps << 8
     sections = [bytes(s) for s in sections]
     if len(sections) != 4:
         raise ValueError("an RGBA file has four sections")
-    head = _HEADER.pack(MAGIC, VERSION, flags, int(h), int(w), int(chunk), alpha.crc, rgb.crc,
+    head = _HEADER.pack(MAGIC, version, flags, int(h), int(w), int(chunk), alpha.crc, rgb.crc,
                         *[len(s) for s in sections])
     return head + b"".join(sections)
 
@@ -98,12 +106,21 @@ def parse_rgba_file(blob, alpha, rgb):
     magic, version, flags, h, w, chunk, crc_a, crc_r, *lens = _HEADER.unpack_from(blob)
     if magic != MAGIC:
         raise RuntimeError("RGBA file: bad magic (not an RGBA file)")
-    if version != VERSION:
+    if version not in (VERSION, VERSION_LANES):
         raise RuntimeError(f"RGBA file: unsupported version {version}")
-    if flags & ~(FLAG_OPAQUE | FLAG_ALPHA_BF16 | FLAG_RGB_BF16):
+    lanes_file = version == VERSION_LANES
+    if lanes_file and not flags & FLAG_LANES:
+        raise RuntimeError("RGBA file: unsupported version 2 without the lanes flag (bit 3): "
+                           "version-2 files hold lanes containers")
+    if flags & ~(FLAG_OPAQUE | FLAG_ALPHA_BF16 | FLAG_RGB_BF16 | (FLAG_LANES if lanes_file else 0)):
         raise RuntimeError(f"RGBA file: unknown flags {flags:#x}")
     if h < 1 or w < 1 or h >= 1 << 24 or w >= 1 << 24 or chunk < 1 or chunk >= 1 << 31:
         raise RuntimeError(f"RGBA file: bad size {h}x{w} or chunk size {chunk}")
+    if lanes_file:
+        try:
+            geometry = _check_lanes(chunk & 255, chunk >> 8)
+        except ValueError as e:
+            raise RuntimeError(f"RGBA file: bad lanes geometry ({e})") from None
     opaque = bool(flags & FLAG_OPAQUE)
     total = HEADER_BYTES + sum(lens)
     if total != len(blob):
@@ -127,17 +144,24 @@ def parse_rgba_file(blob, alpha, rgb):
                                f"encoder's (CRC {info.crc:#010x}, the file says {crc:#010x}): "
                                "other weights")
     hp, wp = anysize.padded_size(h, w)
-    out = {"h": h, "w": w, "canvas": (hp, wp), "chunk": chunk, "opaque": opaque}
+    out = {"h": h, "w": w, "canvas": (hp, wp), "chunk": chunk, "opaque": opaque,
+           "coder": "lanes" if lanes_file else "device"}
     want = dict(zip(SECTIONS, _segments(alpha, hp, wp) + _segments(rgb, hp, wp)))
     pos = HEADER_BYTES
     for name, n in zip(SECTIONS, lens):
         lay = None
         if n:
-            lay = ChunkedLayout(blob[pos:pos + n])
-            if lay.K != chunk or lay.seg_lengths.tolist() != want[name]:
-                raise RuntimeError(f"RGBA file: section {name} has chunk size {lay.K} and "
-                                   f"segments {lay.seg_lengths.tolist()}; a {h}x{w} image needs "
-                                   f"{chunk} and {want[name]}")
+            if lanes_file:
+                lay = LanesLayout(blob[pos:pos + n])
+                have, need = (lay.W, lay.K), geometry
+            else:
+                lay = ChunkedLayout(blob[pos:pos + n])
+                have, need = lay.K, chunk
+            if have != need or lay.seg_lengths.tolist() != want[name]:
+                what = "(lanes, steps)" if lanes_file else "chunk size"
+                raise RuntimeError(f"RGBA file: section {name} has {what} {have} and segments "
+                                   f"{lay.seg_lengths.tolist()}; a {h}x{w} image needs {need} "
+                                   f"and {want[name]}")
         out[name] = lay
         pos += n
     return out
@@ -173,8 +197,9 @@ def _decode_latents(model, z_lays, y_lays, hp, wp, dev, err):
     info = codec_info(model)
     B, zh, zw = len(z_lays), hp // 64, wp // 64
     zseg, yseg = _segments(info, hp, wp)
-    z_dec = MergedChunkedDecoder(z_lays, _starts(B, 1, zseg[0]), dev, err=err)
-    y_dec = MergedChunkedDecoder(y_lays, _starts(B, len(yseg), yseg[0]), dev, err=err)
+    Merged = MergedLanesDecoder if isinstance(z_lays[0], LanesLayout) else MergedChunkedDecoder
+    z_dec = Merged(z_lays, _starts(B, 1, zseg[0]), dev, err=err)
+    y_dec = Merged(y_lays, _starts(B, len(yseg), yseg[0]), dev, err=err)
     z_sym = torch.empty((B, info.z_channels, zh, zw), dtype=torch.int32, device=dev)
     z_dec.decode_segments(0, 1, _z_indexes(info.z_channels, zh * zw, B, dev),
                           model.entropy_bottleneck.device_tables(dev), out=z_sym)
@@ -200,15 +225,24 @@ def _models(masknet, net):
 
 
 @torch.no_grad()
-def encode_rgba(masknet, net, images, chunk=256, debug=None):
+def encode_rgba(masknet, net, images, chunk=256, debug=None, coder="device",
+                lanes=LANES_DEFAULT[0], steps=LANES_DEFAULT[1]):
     """images: what anysize.pack_rgba takes (a list of (h, w, 4) uint8 arrays / tensors, any
     sizes) -> list[bytes], one complete file per image.  ``chunk``: symbols per rANS chunk (see
-    AutoEncoder.compress).  ``debug``: a list that receives, per image, the encoder's symbols
-    and y_hat ({"alpha": {...} or None, "rgb": {"z", "y", "YH"}})."""
+    AutoEncoder.compress).  coder="lanes" writes version-2 files, whose sections are lanes
+    containers of ``lanes`` lanes and ``steps`` steps per group (rgbac/ans.py).  ``debug``: a
+    list that receives, per image, the encoder's symbols and y_hat
+    ({"alpha": {...} or None, "rgb": {"z", "y", "YH"}})."""
     dev = _models(masknet, net)
     chunk = int(chunk)
     if chunk <= 0 or chunk >= 1 << 31:
         raise ValueError("chunk size must be a positive 32-bit number")
+    if coder not in ("device", "lanes"):
+        raise ValueError(f"coder must be 'device' or 'lanes', got {coder!r}")
+    if coder == "lanes":
+        chunk = _check_lanes(lanes, steps)
+        if chunk[1] >= 1 << 23:              # the header field holds lanes | steps << 8 in 31 bits
+            raise ValueError("steps must be below 2^23 in a file")
     dev, sizes, entries, keep = anysize._sources(images, dev, "encode_rgba")
     flags_dev = anysize._opaque(dev, entries)
     flags = flags_dev.cpu().tolist()        # the one read: which sections, which images to masknet
@@ -223,19 +257,22 @@ def encode_rgba(masknet, net, images, chunk=256, debug=None):
         coded = _encode_group(masknet, net, dev, [sizes[k] for k in members],
                               [entries[k] for k in members], [flags[k] for k in members],
                               flags_dev[torch.tensor(members, device=dev)].contiguous(), chunk,
-                              debug is not None)
+                              debug is not None, coder)
         for k, (secs, dbg) in zip(members, coded):
-            files[k] = build_rgba_file(*sizes[k], chunk, bool(flags[k]), info_a, info_r, secs)
+            files[k] = build_rgba_file(*sizes[k], chunk, bool(flags[k]), info_a, info_r, secs,
+                                       coder)
             if debug is not None:
                 debug[k] = dbg
     return files
 
 
-def _encode_group(masknet, net, dev, sizes, entries, opaque, opaque_dev, chunk, want_debug):
+def _encode_group(masknet, net, dev, sizes, entries, opaque, opaque_dev, chunk, want_debug,
+                  coder="device"):
     """One batched coding pass over images that share a canvas (encode_rgba's group body; the
     tiled encoder runs its tiles through it too).  sizes / entries: as anysize._sources returns
     them; opaque: per image, truthy where every alpha byte is 255 (host list), opaque_dev the
-    same as a device int32 tensor (the pack's per-image pad modes).  -> per image
+    same as a device int32 tensor (the pack's per-image pad modes).
+    coder="lanes": lanes containers, ``chunk`` = (lanes, steps).  -> per image
     (its four sections in SECTIONS order, the alpha ones b"" when opaque; its debug record or
     None)."""
     from .models._codec import latent_code
@@ -253,7 +290,8 @@ def _encode_group(masknet, net, dev, sizes, entries, opaque, opaque_dev, chunk, 
         y = net.Encoder.nhwc(rt.to_nhwc(p["masked"], net.compute_dtype), me[1], me[2])
         lat_r = latent_code(net, y=y)
         jobs += _latent_jobs(net, *lat_r[1:])
-    blobs = encode_image_major(jobs, chunk)
+    blobs = (encode_lanes_image_major(jobs, *chunk) if coder == "lanes"
+             else encode_image_major(jobs, chunk))
     out = []
     for j in range(len(sizes)):
         a = nonop.index(j) if j in nonop else None
@@ -283,12 +321,12 @@ def decode_rgba(masknet, net, blobs, debug=None):
     parsed = [parse_rgba_file(b, info_a, info_r) for b in blobs]
     groups = collections.OrderedDict()
     for k, f in enumerate(parsed):
-        groups.setdefault(f["canvas"] + (f["chunk"],), []).append(k)
+        groups.setdefault(f["canvas"] + (f["coder"], f["chunk"]), []).append(k)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     outs = [None] * len(blobs)
     if debug is not None:
         debug[:] = [None] * len(blobs)
-    for (hp, wp, _), members in groups.items():
+    for (hp, wp, _, _), members in groups.items():
         fs = [parsed[k] for k in members]
         x_hat, alpha, dbgs = _decode_group(masknet, net, fs, hp, wp, dev, err, debug is not None)
         rgba = anysize.unpack_rgba(x_hat, alpha, [(f["h"], f["w"]) for f in fs])

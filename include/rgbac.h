@@ -1066,6 +1066,62 @@ int rgbac_alpha_exact_decode(int batch, const rgbac_image_desc* descs, int pixel
                              const int32_t* counts, const uint32_t* payload,
                              int64_t payload_words, int32_t* err, void* stream);
 
+/* Lane-interleaved rANS coder (csrc/rans_lanes.hip over csrc/rans_lanes.h, DESIGN.md section
+ * 25): the "lanes" stream format of compress / decompress (coder="lanes").  The symbol sequence
+ * is cut into groups of at most W * K symbols (W in {8, 16, 32, 64} lanes, K steps); symbol j of
+ * a group belongs to lane j % W at step j / W.  A lane is a 32-bit rANS state with byte
+ * renormalisation over the tables, escape symbol and bypass digits of the coder above; all lanes
+ * of a group share one byte stream ordered by (step, record, round, lane).  A group's bytes are
+ * the W final states (little-endian u32) and then the stream.  Group g covers symbols
+ * [group_start[g], group_start[g] + group_len[g]) of the container's sequence; symbols / indexes
+ * / out address symbol sym_base of it and hold nsym entries.  A wave codes 64 / W groups at
+ * once.  All pointers are device pointers; payload is 4-byte aligned; err as for
+ * rgbac_rans_chunk_* (an erring group decodes to zeros from the step of the error on; a group
+ * that does not end with every byte read and every lane back at its start value is code 3).
+ * Tables of at most RGBAC_LANES_LDS_ENTRIES entries (ncdf * cdf_stride) are staged in LDS.
+ *   rgbac_rans_lanes_sizes : counts[g] = bytes of group g (the state machine without stores)
+ *   rgbac_rans_lanes_encode: stores group g's bytes into payload[ends[g] - counts[g], ends[g])
+ *   rgbac_rans_lanes_decode: group g's bytes are payload[byte_off[g], byte_off[g] + counts[g]);
+ *                            payload_bytes is a multiple of 4
+ * The *_host entry points run the same lane functions in CPU loops on host pointers (tests,
+ * streams without a GPU; the device path never calls them); rgbac_rans_lanes_encode_host packs
+ * the groups in order; payload == NULL returns counts and *total_bytes only. */
+#define RGBAC_LANES_LDS_ENTRIES 24576
+int rgbac_rans_lanes_sizes(const int32_t* symbols, const int32_t* indexes, int64_t nsym,
+                           int64_t sym_base, const int64_t* group_start,
+                           const int64_t* group_len, int64_t ngroups, int W, int K,
+                           const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                           const int32_t* offsets, int ncdf, int32_t* counts, int32_t* err,
+                           void* stream);
+int rgbac_rans_lanes_encode(const int32_t* symbols, const int32_t* indexes, int64_t nsym,
+                            int64_t sym_base, const int64_t* group_start,
+                            const int64_t* group_len, int64_t ngroups, int W, int K,
+                            const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                            const int32_t* offsets, int ncdf, const int32_t* counts,
+                            const int64_t* ends, uint8_t* payload, int64_t payload_bytes,
+                            int32_t* err, void* stream);
+int rgbac_rans_lanes_decode(const uint8_t* payload, int64_t payload_bytes,
+                            const int64_t* byte_off, const int32_t* counts,
+                            const int32_t* indexes, int64_t nsym, int64_t sym_base,
+                            const int64_t* group_start, const int64_t* group_len,
+                            int64_t ngroups, int W, int K, const int32_t* cdfs, int cdf_stride,
+                            const int32_t* cdf_sizes, const int32_t* offsets, int ncdf,
+                            int32_t* out, int32_t* err, void* stream);
+int rgbac_rans_lanes_encode_host(const int32_t* symbols, const int32_t* indexes, int64_t nsym,
+                                 int64_t sym_base, const int64_t* group_start,
+                                 const int64_t* group_len, int64_t ngroups, int W, int K,
+                                 const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                                 const int32_t* offsets, int ncdf, int32_t* counts,
+                                 uint8_t* payload, int64_t payload_bytes, int64_t* total_bytes,
+                                 int32_t* err);
+int rgbac_rans_lanes_decode_host(const uint8_t* payload, int64_t payload_bytes,
+                                 const int64_t* byte_off, const int32_t* counts,
+                                 const int32_t* indexes, int64_t nsym, int64_t sym_base,
+                                 const int64_t* group_start, const int64_t* group_len,
+                                 int64_t ngroups, int W, int K, const int32_t* cdfs,
+                                 int cdf_stride, const int32_t* cdf_sizes,
+                                 const int32_t* offsets, int ncdf, int32_t* out, int32_t* err);
+
 #ifdef __cplusplus
 }
 #endif
