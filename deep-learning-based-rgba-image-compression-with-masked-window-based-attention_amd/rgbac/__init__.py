@@ -3,5 +3,7 @@
 Drop-in mirrors of the reference modules live in ``rgbac.models`` and
 ``rgbac.layers``; the compute is librgbac_hip.so (C ABI: include/rgbac.h)."""
 from . import _lib  # noqa: F401
+from .rgbalossless import (decode_rgba_lossless, encode_rgba_lossless,  # noqa: F401
+                           encode_rgba_lossless_host, parse_rgba_lossless)
 
 __version__ = "0.1.0"

@@ -118,6 +118,8 @@ PAD_MODES = dict(transparent=0, replicate=1)   # enum rgbac_pad_mode
 OPAQUE_BLOCKS = 32                              # RGBAC_OPAQUE_BLOCKS
 # RGBAC_ALPHA_BLOCK, _GROUP, _CONTEXTS, _HIST_BLOCKS, _TABLE_U16
 ALPHA_BLOCK, ALPHA_GROUP, ALPHA_CONTEXTS, ALPHA_HIST_BLOCKS, ALPHA_TABLE_U16 = 16, 64, 5, 16, 1288
+# RGBAC_COLOR_CHANNELS, _HIST_BLOCKS, _TABLE_U16
+COLOR_CHANNELS, COLOR_HIST_BLOCKS, COLOR_TABLE_U16 = 3, 16, 3856
 
 _VP, _I32, _I64, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 _D = ctypes.c_double
@@ -295,6 +297,14 @@ SIGNATURES = {
     "rgbac_alpha_exact_encode": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP,
                                  _I64, _VP, _VP],
     "rgbac_alpha_exact_decode": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP,
+                                 _I64, _VP, _VP],
+    # lossless colour of packed RGBA (csrc/color_exact.hip)
+    "rgbac_color_exact_classify": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP],
+    "rgbac_color_exact_tables": [_I32, _VP, _I32, _VP, _I32, _VP, _VP, _VP, _VP, _VP],
+    "rgbac_color_exact_sizes": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP],
+    "rgbac_color_exact_encode": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP,
+                                 _I64, _VP, _VP],
+    "rgbac_color_exact_decode": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP,
                                  _I64, _VP, _VP],
 }
 _RESTYPE = {"rgbac_last_error": ctypes.c_char_p, "rgbac_rans_encoder_bound": ctypes.c_int64,

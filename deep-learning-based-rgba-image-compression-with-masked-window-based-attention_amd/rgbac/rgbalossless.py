@@ -1,0 +1,369 @@
+"""Lossless RGBA files (``RGAL``): exact alpha beside exact colour, both coded on the device.
+
+``encode_rgba_lossless`` takes a ragged batch of packed uint8 RGBA images and returns one
+self-contained file per image; ``decode_rgba_lossless`` takes any list of files in any order and
+returns the images bit for bit, except that a pixel nobody can see (alpha 0) comes back with
+R = G = B = 0 unless the file was written with ``keep_hidden``.  No model is involved.  GPU only:
+a CPU device or a missing library raises.
+
+The alpha plane is an ``RGAP`` blob of rgbac.alphaexact, unchanged.  The colour is coded by
+csrc/color_exact.hip: subtract-green (Y = G, Cr = (R - G + 128) & 255, Cb = (B - G + 128) & 255),
+MED prediction inside 16 x 16 blocks over the neighbours that are visible, 15 static tables per
+image (channel * 5 + context), one rANS chunk per block and channel that is not constant.  Model,
+format and launches: DESIGN.md section 26.
+
+File, little-endian:
+    "RGAL", u16 version (1), u16 flags (bit 0: keep_hidden), u32 h, u32 w, u32 alpha bytes, u32
+    colour bytes; the RGAP blob; the colour section: u32 chunks, u32 payload words; 15 tables in
+    the RGAP table form, channel-major; one u32 class word per block, row-major (bit 0 hidden,
+    bits 1-3 channel Y / Cr / Cb constant, bits 8-15 / 16-23 / 24-31 the constants); one u16 word
+    count per chunk (block-major, Y, Cr, Cb); the payload, u32 words.
+"""
+import struct
+
+import numpy as np
+import torch
+
+from . import _lib, alphaexact, anysize
+from .alphaexact import BLOCK, MAX_SIDE, SPARSE_MAX, TOTAL, block_grid, normalise_counts
+from .ans import _raise_code, _upload
+
+MAGIC = b"RGAL"
+VERSION = 1
+FLAG_KEEP_HIDDEN = 1
+NCH = _lib.COLOR_CHANNELS
+NCTX = alphaexact.NCTX
+NTAB = NCH * NCTX                     # 15 tables: channel * 5 + context
+_HEADER = struct.Struct("<4sHHIIII")
+HEADER_BYTES = _HEADER.size           # 24
+_HIDDEN = 1                           # the class word of a block without a visible pixel
+
+
+def _chunk_mask(cls):
+    """class words (N,) -> bool (N, 3): block k has a chunk for channel c."""
+    cls = np.asarray(cls).astype(np.int64)
+    return ((cls[:, None] & 1) == 0) & (((cls[:, None] >> (1 + np.arange(NCH))) & 1) == 0)
+
+
+def device_table(freqs):
+    """(15, 256) frequencies -> the uint16[3856] table the kernels stage in LDS: exclusive sums
+    mod 2^16, the last symbol with a frequency per table (-1: empty), one zero."""
+    f = np.asarray(freqs, dtype=np.int64).reshape(NTAB, 256)
+    tab = np.zeros(_lib.COLOR_TABLE_U16, dtype=np.uint16)
+    tab[:NTAB * 256] = ((np.cumsum(f, axis=1) - f) & 0xFFFF).reshape(-1)
+    for c in range(NTAB):
+        nz = np.flatnonzero(f[c])
+        tab[NTAB * 256 + c] = np.int16(nz[-1] if nz.size else -1).view(np.uint16)
+    return tab
+
+
+def host_tables(freqs):
+    """(15, 256) frequencies -> the rgbac.ans.CdfTables the host chunk coder takes (rows of 258
+    entries, as alphaexact.host_tables)."""
+    from .ans import CdfTables
+    f = np.asarray(freqs, dtype=np.int64).reshape(NTAB, 256)
+    cdfs = np.zeros((NTAB, 258), dtype=np.int32)
+    cdfs[:, 1:257] = np.cumsum(f, axis=1)
+    cdfs[:, 257] = cdfs[:, 256]
+    return CdfTables(cdfs, [258] * NTAB, [0] * NTAB)
+
+
+def build_colour(freqs, cls, counts, payload):
+    """The pieces of one image's colour section -> bytes.  freqs (15, 256); cls: the blocks'
+    class words; counts: the chunks' word counts in chunk order; payload: their words."""
+    counts = np.asarray(counts)
+    return b"".join(
+        [struct.pack("<II", counts.size, len(payload))]
+        + [alphaexact._pack_table(np.asarray(f, dtype=np.int64)) for f in freqs]
+        + [np.asarray(cls).astype("<u4").tobytes(), counts.astype("<u2").tobytes(),
+           np.asarray(payload).astype("<u4").tobytes()])
+
+
+def build_rgba_lossless(h, w, keep_hidden, alpha, colour):
+    return _HEADER.pack(MAGIC, VERSION, FLAG_KEEP_HIDDEN if keep_hidden else 0, h, w, len(alpha),
+                        len(colour)) + alpha + colour
+
+
+def parse_rgba_lossless(blob):
+    """bytes -> {"h", "w", "keep_hidden", "alpha": the parsed RGAP blob, "freqs" (15, 256) int64,
+    "cls" uint32 per block, "counts" int32 (blocks, 3) (0 where there is no chunk), "payload"
+    uint32}.  Pure host code; raises RuntimeError on anything wrong: bad magic, version, flags or
+    size; truncation or over-length; section lengths that disagree; an alpha blob that
+    parse_alpha_planes rejects or of another size; tables that are not fixed points of
+    normalise_counts; class words with reserved bits set, a hidden word that is not 1 or a value
+    byte under a clear flag; a chunk table whose length is not what the class words imply; word
+    counts outside [2, block pixels / 2 + 3] or that do not sum to the payload."""
+    blob = bytes(blob)
+
+    def bad(msg):
+        return RuntimeError(f"RGAL file: {msg}")
+
+    if len(blob) < HEADER_BYTES:
+        raise bad(f"truncated ({len(blob)} bytes, the header has {HEADER_BYTES})")
+    magic, version, flags, h, w, alpha_len, colour_len = _HEADER.unpack_from(blob)
+    if magic != MAGIC:
+        raise bad("bad magic (not an RGAL file)")
+    if version != VERSION:
+        raise bad(f"unsupported version {version}")
+    if flags & ~FLAG_KEEP_HIDDEN:
+        raise bad(f"unknown flags {flags:#x}")
+    if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+        raise bad(f"bad size {h}x{w}")
+    total = HEADER_BYTES + alpha_len + colour_len
+    if total != len(blob):
+        raise bad(f"{'truncated' if len(blob) < total else 'over-long'}: the section lengths say "
+                  f"{total} bytes, the file has {len(blob)}")
+    alpha = alphaexact.parse_alpha_planes(blob[HEADER_BYTES:HEADER_BYTES + alpha_len])
+    if (alpha["h"], alpha["w"]) != (h, w):
+        raise bad(f"the alpha plane is {alpha['h']}x{alpha['w']}, the image {h}x{w}")
+    sec = blob[HEADER_BYTES + alpha_len:]
+    pos = 0
+
+    def take(n, what):
+        nonlocal pos
+        if pos + n > len(sec):
+            raise bad(f"the colour section is truncated in the {what}")
+        pos += n
+        return sec[pos - n:pos]
+
+    nchunks, nwords = struct.unpack("<II", take(8, "header"))
+    freqs = np.zeros((NTAB, 256), dtype=np.int64)
+    for c in range(NTAB):
+        n = struct.unpack("<H", take(2, "tables"))[0]
+        if n > 256 or n == 1:
+            raise bad(f"table {c} lists {n} symbols")
+        if n > SPARSE_MAX:
+            freqs[c] = np.frombuffer(take(512, "tables"), dtype="<u2")
+            if int((freqs[c] > 0).sum()) != n:
+                raise bad(f"table {c}: the symbol count disagrees with its frequencies")
+        elif n:
+            rec = np.frombuffer(take(3 * n, "tables"), dtype=np.dtype([("s", "u1"), ("f", "<u2")]))
+            if (np.diff(rec["s"].astype(np.int64)) <= 0).any() or (rec["f"] == 0).any():
+                raise bad(f"table {c}: symbols out of order or without a frequency")
+            freqs[c, rec["s"]] = rec["f"]
+        if n and int(freqs[c].sum()) != TOTAL:
+            raise bad(f"table {c} sums to {int(freqs[c].sum())}, not 2^16")
+        if (normalise_counts(freqs[c]) != freqs[c]).any():
+            raise bad(f"table {c} is not a normalised table")
+    npix = block_grid(h, w)[2]
+    cls = np.frombuffer(take(4 * npix.size, "class table"), dtype="<u4").astype(np.uint32)
+    if (cls & 0xF0).any():
+        raise bad("class table: reserved bits set")
+    if ((cls & 1) & (cls != _HIDDEN)).any():
+        raise bad("class table: a hidden block's word is not 1")
+    const = ((cls[:, None].astype(np.int64) >> (1 + np.arange(NCH))) & 1) == 1
+    value = (cls[:, None].astype(np.int64) >> (8 + 8 * np.arange(NCH))) & 255
+    if (value[~const] != 0).any():
+        raise bad("class table: a value under a clear constant flag")
+    has = _chunk_mask(cls)
+    if int(has.sum()) != nchunks:
+        raise bad(f"the class table implies {int(has.sum())} chunks, the chunk table has "
+                  f"{nchunks}")
+    cnt = np.frombuffer(take(2 * nchunks, "chunk table"), dtype="<u2").astype(np.int64)
+    # a chunk holds its two state words and at most 16 bits per symbol
+    if (cnt < 2).any() or (cnt > np.broadcast_to(npix[:, None], has.shape)[has] // 2 + 3).any():
+        raise bad("chunk table: a chunk's word count is impossible for its block")
+    if int(cnt.sum()) != nwords:
+        raise bad(f"the chunk table sums to {int(cnt.sum())} words, the section says {nwords}")
+    payload = np.frombuffer(take(4 * nwords, "payload"), dtype="<u4").astype(np.uint32)
+    if pos != len(sec):
+        raise bad(f"the colour section is over-long: {len(sec) - pos} bytes after the payload")
+    counts = np.zeros(has.shape, dtype=np.int32)
+    counts[has] = cnt
+    return {"h": h, "w": w, "keep_hidden": bool(flags & FLAG_KEEP_HIDDEN), "alpha": alpha,
+            "freqs": freqs, "cls": cls, "counts": counts, "payload": payload}
+
+
+# ---- the CPU twin: the model in numpy, the chunks by the host chunk coder (rgbac.ans)
+def _shift(a, dy, dx):
+    """a moved down / right by (dy, dx) along its last two axes, zeros coming in."""
+    out = np.zeros_like(a)
+    h, w = a.shape[-2:]
+    out[..., dy:, dx:] = a[..., :h - dy, :w - dx]
+    return out
+
+
+def model_symbols(image, keep_hidden=False):
+    """(h, w, 4) uint8 -> (symbols (3, h, w), contexts (3, h, w), visible (h, w)): the model of
+    DESIGN.md section 26 for every pixel of the planes Y, Cr, Cb, each inside its own 16 x 16
+    block; entries of hidden pixels mean nothing."""
+    a = np.asarray(image).astype(np.int64)
+    h, w = a.shape[:2]
+    vis = np.ones((h, w), dtype=bool) if keep_hidden else a[..., 3] != 0
+    g = a[..., 1]
+    v = np.stack([g, (a[..., 0] - g + 128) & 255, (a[..., 2] - g + 128) & 255])
+    inr = np.broadcast_to((np.arange(h) % BLOCK != 0)[:, None], (h, w))
+    inc = np.broadcast_to((np.arange(w) % BLOCK != 0)[None, :], (h, w))
+    eL, eU, eD = _shift(vis, 0, 1) & inc, _shift(vis, 1, 0) & inr, _shift(vis, 1, 1) & inr & inc
+    L, U, D = _shift(v, 0, 1), _shift(v, 1, 0), _shift(v, 1, 1)
+    D = np.where(eD, D, L)
+    lo, hi = np.minimum(L, U), np.maximum(L, U)
+    med = np.where(D >= hi, lo, np.where(D <= lo, hi, L + U - D))
+    d = np.maximum(hi, D) - np.minimum(lo, D)
+    bins = (d > 0).astype(np.int64) + (d > 8) + (d > 64)
+    one = np.where(eL, L, np.where(eU, U, _shift(v, 1, 1)))
+    both, some = eL & eU, eL | eU | eD
+    pred = np.where(both, med, np.where(some, one, 0))
+    ctx = np.where(both, bins, np.where(some, 0, 4))
+    return ((v - pred) & 255).astype(np.int32), ctx.astype(np.int32), vis
+
+
+def encode_rgba_lossless_host(image, keep_hidden=False):
+    """encode_rgba_lossless for one image on the CPU: the kernels' byte-level reference (not a
+    fallback; the device path never calls it)."""
+    from .ans import encode_table_host
+    a = np.ascontiguousarray(np.asarray(image, dtype=np.uint8))
+    if a.ndim != 3 or a.shape[2] != 4 or a.size == 0 or max(a.shape[:2]) > MAX_SIDE:
+        raise ValueError(f"encode_rgba_lossless_host: expected (H, W, 4) uint8 RGBA, got {a.shape}")
+    h, w = a.shape[:2]
+    sym, ctx, vis = model_symbols(a, keep_hidden)
+    g = a[..., 1].astype(np.int64)
+    planes = [g, (a[..., 0] - g + 128) & 255, (a[..., 2] - g + 128) & 255]
+    cls, s, t, lens = [], [], [], []
+    blocks = [(r, c) for r in range(0, h, BLOCK) for c in range(0, w, BLOCK)]
+    for r, c in blocks:
+        at = (slice(r, r + BLOCK), slice(c, c + BLOCK))
+        m = vis[at]
+        if not m.any():
+            cls.append(_HIDDEN)
+            continue
+        word = 0
+        for ch in range(NCH):
+            vals = planes[ch][at][m]                     # raster order
+            if (vals == vals[0]).all():
+                word |= (2 << ch) | (int(vals[0]) << (8 + 8 * ch))
+            else:
+                s.append(sym[ch][at][m])
+                t.append(ctx[ch][at][m] + NCTX * ch)
+                lens.append(vals.size)
+        cls.append(word)
+    freqs = np.zeros((NTAB, 256), dtype=np.int64)
+    counts, payload = np.zeros(0, np.int32), np.zeros(0, np.uint32)
+    if lens:
+        s, t, lens = np.concatenate(s), np.concatenate(t), np.asarray(lens, dtype=np.int64)
+        for k in range(NTAB):
+            freqs[k] = normalise_counts(np.bincount(s[t == k], minlength=256))
+        table = np.stack([np.cumsum(lens) - lens, lens])
+        words = encode_table_host(s, t, host_tables(freqs), table, BLOCK * BLOCK)
+        counts, payload = words[:lens.size], words[lens.size:].view(np.uint32)
+    return build_rgba_lossless(h, w, keep_hidden, alphaexact.encode_alpha_plane_host(a[..., 3]),
+                               build_colour(freqs, np.asarray(cls, dtype=np.uint32), counts,
+                                            payload))
+
+
+# ---- launches
+def _alpha_entries(entries):
+    """RGBA descriptor entries -> the same rectangles' alpha bytes, 4 bytes apart."""
+    return [(ptr + 3, h, w, stride) for ptr, h, w, stride in entries]
+
+
+def _args(wk, keep_hidden, grouped):
+    """The leading arguments of the rgbac_color_exact_* calls from alphaexact's geometry."""
+    head = (wk.B, wk._descs.data_ptr(), int(keep_hidden))
+    mid = (wk.ngroups, wk._groups.data_ptr()) if grouped else ()
+    return head + mid + (wk._base.data_ptr(), wk.N)
+
+
+def _encode_colour(dev, sizes, entries, keep_hidden):
+    """The five launches over a ragged batch (classify, histogram, normalise, sizes, encode) and
+    the two host reads -> one colour section per image."""
+    wk = alphaexact._Work(sizes, entries, 4, dev)
+    B, N, nf = wk.B, wk.N, NTAB * 256
+    meta = torch.empty((1 + NCH) * N + B * nf, dtype=torch.int32, device=dev)
+    cls, counts, freqs = meta[:N], meta[N:(1 + NCH) * N], meta[(1 + NCH) * N:]
+    partials = torch.empty(B * _lib.COLOR_HIST_BLOCKS * nf, dtype=torch.int32, device=dev)
+    tables = torch.empty(B * _lib.COLOR_TABLE_U16, dtype=torch.int16, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    plain, grouped = _args(wk, keep_hidden, False), _args(wk, keep_hidden, True)
+    _lib.call("rgbac_color_exact_classify", *grouped, cls.data_ptr(), wk.stream)
+    _lib.call("rgbac_color_exact_tables", *plain, cls.data_ptr(), partials.data_ptr(),
+              freqs.data_ptr(), tables.data_ptr(), wk.stream)
+    _lib.call("rgbac_color_exact_sizes", *grouped, cls.data_ptr(), tables.data_ptr(),
+              counts.data_ptr(), err.data_ptr(), wk.stream)
+    ends = torch.cumsum(counts, 0, dtype=torch.int64)
+    host = meta.cpu().numpy()                                       # the sizes: one read
+    h_cls = host[:N].view(np.uint32)
+    h_counts = host[N:(1 + NCH) * N].reshape(N, NCH)
+    h_freqs = host[(1 + NCH) * N:].reshape(B, NTAB, 256)
+    cut = np.concatenate([[0], np.cumsum(h_counts.sum(axis=1, dtype=np.int64))])
+    total = int(cut[-1])
+    words = torch.empty(total + 1, dtype=torch.int32, device=dev)
+    if total:
+        _lib.call("rgbac_color_exact_encode", *grouped, cls.data_ptr(), tables.data_ptr(),
+                  counts.data_ptr(), ends.data_ptr(), words.data_ptr(), total, err.data_ptr(),
+                  wk.stream)
+    words[total:].copy_(err)
+    words = words.cpu().numpy()                                     # the words: one copy
+    _raise_code("encode_rgba_lossless", int(words[total]))
+    out = []
+    for b in range(B):
+        lo, hi = int(wk.base[b]), int(wk.base[b + 1])
+        c = h_cls[lo:hi]
+        out.append(build_colour(h_freqs[b], c, h_counts[lo:hi][_chunk_mask(c)],
+                                words[int(cut[lo]):int(cut[hi])].view(np.uint32)))
+    return out
+
+
+def encode_rgba_lossless(images, keep_hidden=False, device="cuda"):
+    """images: a list of (h, w, 4) uint8 RGBA images of any sizes; GPU tensors are read in place,
+    views into larger buffers included -> list[bytes], one RGAL file per image.  A hidden pixel
+    (alpha 0) decodes to R = G = B = 0 and its colour bytes do not reach the file;
+    ``keep_hidden`` codes every pixel's colour.  A file does not depend on the images coded with
+    it."""
+    dev = anysize._gpu_device(device)
+    _lib.load()
+    dev, sizes, entries, keep = anysize._sources(images, dev, "encode_rgba_lossless")
+    if max(max(s) for s in sizes) > MAX_SIDE:
+        raise ValueError(f"encode_rgba_lossless: an image side is at most {MAX_SIDE}")
+    keep_hidden = bool(keep_hidden)
+    alpha = alphaexact._encode(dev, sizes, _alpha_entries(entries), 4)
+    colour = _encode_colour(dev, sizes, entries, keep_hidden)
+    return [build_rgba_lossless(h, w, keep_hidden, a, c)
+            for (h, w), a, c in zip(sizes, alpha, colour)]
+
+
+def _decode_colour(parsed, entries, keep_hidden, dev, err):
+    """One launch for parsed files that share ``keep_hidden`` onto the images ``entries``
+    describe (their alpha bytes in place); errors land in ``err``."""
+    sizes = [(f["h"], f["w"]) for f in parsed]
+    wk = alphaexact._Work(sizes, entries, 4, dev)
+    counts = np.concatenate([f["counts"].reshape(-1) for f in parsed])
+    pbase = np.concatenate([[0], np.cumsum([f["payload"].size for f in parsed])])
+    off = np.concatenate([pbase[i] + np.cumsum(f["counts"].reshape(-1), dtype=np.int64)
+                          - f["counts"].reshape(-1) for i, f in enumerate(parsed)])
+    payload = np.concatenate([f["payload"] for f in parsed] + [np.zeros(1, dtype=np.uint32)])
+    cls = np.concatenate([f["cls"] for f in parsed])
+    ints = _upload(np.concatenate([cls.view(np.int32), counts, payload.view(np.int32)])
+                   .astype(np.int32), dev)
+    off = _upload(off.astype(np.int64), dev)
+    tables = _upload(np.concatenate([device_table(f["freqs"]) for f in parsed]).view(np.int16),
+                     dev)
+    N = wk.N
+    _lib.call("rgbac_color_exact_decode", *_args(wk, keep_hidden, True), ints[:N].data_ptr(),
+              tables.data_ptr(), off.data_ptr(), ints[N:(1 + NCH) * N].data_ptr(),
+              ints[(1 + NCH) * N:].data_ptr(), int(pbase[-1]), err.data_ptr(), wk.stream)
+
+
+def decode_rgba_lossless(blobs, device="cuda"):
+    """blobs: files from encode_rgba_lossless, any number, any order -> list of (h, w, 4) uint8
+    GPU tensors in the same order.  Every file is parsed and validated on the host before any
+    launch (RuntimeError); one plane-decoder launch puts all alpha planes into the outputs' alpha
+    bytes, one colour launch (two when files with and without keep_hidden are mixed) fills in
+    R, G, B on the same stream; the one error word is read once at the end."""
+    blobs = list(blobs)
+    if not blobs:
+        raise ValueError("decode_rgba_lossless: no files")
+    parsed = [parse_rgba_lossless(b) for b in blobs]
+    dev = anysize._gpu_device(device)
+    _lib.load()
+    outs = [torch.empty((f["h"], f["w"], 4), dtype=torch.uint8, device=dev) for f in parsed]
+    dev = outs[0].device
+    entries = [(t.data_ptr(), f["h"], f["w"], t.stride(0)) for t, f in zip(outs, parsed)]
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    alphaexact._decode([f["alpha"] for f in parsed], _alpha_entries(entries), 4, dev, err)
+    for flag in (False, True):
+        ks = [k for k, f in enumerate(parsed) if f["keep_hidden"] == flag]
+        if ks:
+            _decode_colour([parsed[k] for k in ks], [entries[k] for k in ks], flag, dev, err)
+    _raise_code("RGAL file decode", int(err.item()))
+    return outs

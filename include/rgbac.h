@@ -1066,6 +1066,62 @@ int rgbac_alpha_exact_decode(int batch, const rgbac_image_desc* descs, int pixel
                              const int32_t* counts, const uint32_t* payload,
                              int64_t payload_words, int32_t* err, void* stream);
 
+/* Lossless colour of packed RGBA (csrc/color_exact.hip, rgbac/rgbalossless.py, DESIGN.md section
+ * 26): the colour half of an RGAL file, beside the alpha-plane coder above.  A pixel is visible
+ * if its alpha is not 0, or always with keep_hidden = 1; hidden pixels are not coded and decode
+ * to R = G = B = 0.  Visible pixels become Y = G, Cr = (R - G + 128) & 255, Cb = (B - G + 128) &
+ * 255; each of the three planes is predicted inside the alpha coder's 16 x 16 blocks by MED over
+ * the neighbours that exist (inside the block and visible) and coded with table channel * 5 +
+ * context of its image: 15 tables per image, the alpha coder's frequency rule.  The model is
+ * fixed by the format: see csrc/color_exact.hip.
+ *   descs: DEVICE array of `batch` rgbac_image_desc, ptr = the first RGBA pixel, 4-byte aligned,
+ *     row_stride_bytes a multiple of 4; every pixel is read and written as one dword.
+ *   block_base, groups, total_blocks (below 2^29): as for rgbac_alpha_exact_*.
+ *   cls: DEVICE uint32[total_blocks]: bit 0 hidden (the word is 1), bits 1-3 channel Y / Cr / Cb
+ *     constant over the block's visible pixels, bits 8-15 / 16-23 / 24-31 that constant.
+ *   counts, ends, word_off: three entries per block, entry 3 * block + channel: the chunks lie
+ *     block-major, Y, Cr, Cb; a hidden block and a constant channel have no chunk (count 0).
+ *   tables: DEVICE uint16[batch * RGBAC_COLOR_TABLE_U16], 4-byte aligned; per image 15 x 256
+ *     exclusive sums (mod 2^16), then per table the last symbol with a frequency as int16 (-1:
+ *     empty), then one zero.
+ * rgbac_color_exact_classify: cls for every block, one launch.
+ * rgbac_color_exact_tables: two launches; partials: DEVICE uint32[batch *
+ *   RGBAC_COLOR_HIST_BLOCKS * 3840] (no initial contents needed, summed in index order), freqs:
+ *   DEVICE int32[batch * 3840].
+ * rgbac_color_exact_sizes / _encode: as rgbac_alpha_exact_sizes / _encode, per chunk.
+ * rgbac_color_exact_decode: one launch, after the alpha bytes of the destination are in place
+ *   (they say who is visible).  Rewrites every pixel of every image as alpha | decoded RGB.
+ *   Every read is bounded as for rgbac_alpha_exact_decode.  Code 3 (corrupt) also for a class
+ *   word that says hidden over a block with a visible pixel or the reverse, a symbol in an empty
+ *   context and a word count impossible for the chunk's visible pixels; such a block decodes to
+ *   RGB 0.  A bad descriptor or group writes nothing (code 5). */
+#define RGBAC_COLOR_CHANNELS 3
+#define RGBAC_COLOR_HIST_BLOCKS 16
+#define RGBAC_COLOR_TABLE_U16 3856
+int rgbac_color_exact_classify(int batch, const rgbac_image_desc* descs, int keep_hidden,
+                               int ngroups, const rgbac_alpha_group* groups,
+                               const int32_t* block_base, int total_blocks, uint32_t* cls,
+                               void* stream);
+int rgbac_color_exact_tables(int batch, const rgbac_image_desc* descs, int keep_hidden,
+                             const int32_t* block_base, int total_blocks, const uint32_t* cls,
+                             uint32_t* partials, int32_t* freqs, uint16_t* tables, void* stream);
+int rgbac_color_exact_sizes(int batch, const rgbac_image_desc* descs, int keep_hidden,
+                            int ngroups, const rgbac_alpha_group* groups,
+                            const int32_t* block_base, int total_blocks, const uint32_t* cls,
+                            const uint16_t* tables, int32_t* counts, int32_t* err, void* stream);
+int rgbac_color_exact_encode(int batch, const rgbac_image_desc* descs, int keep_hidden,
+                             int ngroups, const rgbac_alpha_group* groups,
+                             const int32_t* block_base, int total_blocks, const uint32_t* cls,
+                             const uint16_t* tables, const int32_t* counts, const int64_t* ends,
+                             uint32_t* payload, int64_t payload_words, int32_t* err,
+                             void* stream);
+int rgbac_color_exact_decode(int batch, const rgbac_image_desc* descs, int keep_hidden,
+                             int ngroups, const rgbac_alpha_group* groups,
+                             const int32_t* block_base, int total_blocks, const uint32_t* cls,
+                             const uint16_t* tables, const int64_t* word_off,
+                             const int32_t* counts, const uint32_t* payload,
+                             int64_t payload_words, int32_t* err, void* stream);
+
 /* Lane-interleaved rANS coder (csrc/rans_lanes.hip over csrc/rans_lanes.h, DESIGN.md section
  * 25): the "lanes" stream format of compress / decompress (coder="lanes").  The symbol sequence
  * is cut into groups of at most W * K symbols (W in {8, 16, 32, 64} lanes, K steps); symbol j of
