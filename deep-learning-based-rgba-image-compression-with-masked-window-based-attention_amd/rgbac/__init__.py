@@ -5,5 +5,7 @@ Drop-in mirrors of the reference modules live in ``rgbac.models`` and
 from . import _lib  # noqa: F401
 from .rgbalossless import (decode_rgba_lossless, encode_rgba_lossless,  # noqa: F401
                            encode_rgba_lossless_host, parse_rgba_lossless)
+from .rgbanear import (decode_rgba_near, encode_rgba_near, encode_rgba_near_host,  # noqa: F401
+                       parse_rgba_near)
 
 __version__ = "0.1.0"

@@ -1122,6 +1122,50 @@ int rgbac_color_exact_decode(int batch, const rgbac_image_desc* descs, int keep_
                              const int32_t* counts, const uint32_t* payload,
                              int64_t payload_words, int32_t* err, void* stream);
 
+/* Near-lossless colour of packed RGBA (csrc/color_near.hip, rgbac/rgbanear.py, DESIGN.md section
+ * 28): the colour half of an RGAN file.  Blocks, groups, visibility, contexts, tables, chunk
+ * arrays and the class word layout are rgbac_color_exact_*'s; the planes are G, R, B, predicted
+ * in a closed loop from RECONSTRUCTED neighbours (chroma relative to the reconstructed green),
+ * the prediction error is quantised with step 2 delta + 1, and every visible colour byte decodes
+ * within +-delta.  A channel whose visible values span at most 2 delta in a block is constant at
+ * (min + max) >> 1.  The model is fixed by the format: see csrc/color_near.hip.
+ *   modes: DEVICE int32[batch], per image: bits 0-7 delta in [1, RGBAC_NEAR_MAX_ERROR], bit 8
+ *     (RGBAC_NEAR_KEEP_HIDDEN) keep_hidden; any other value makes the image's groups report code 5
+ *     and touch nothing.
+ *   descs: for _settle the source images; for _tables, _sizes and _encode the SETTLED images that
+ *     _settle wrote; for _decode the destinations.  Layout rules as for rgbac_color_exact_*.
+ * rgbac_color_near_settle: one launch: cls for every block, and the reconstruction of every
+ *   image (alpha | R^ G^ B^, hidden pixels 0) into `settled`: DEVICE array of `batch`
+ *   descriptors of the same sizes as descs.  A block is settled by 16 lanes as a 31-step
+ *   anti-diagonal wavefront.
+ * rgbac_color_near_tables / _sizes / _encode: as rgbac_color_exact_*, over the settled images.
+ * rgbac_color_near_decode: as rgbac_color_exact_decode; code 3 (corrupt) also for a symbol whose
+ *   |q| exceeds (255 + delta) div (2 delta + 1). */
+#define RGBAC_NEAR_MAX_ERROR 16
+#define RGBAC_NEAR_KEEP_HIDDEN 256
+int rgbac_color_near_settle(int batch, const rgbac_image_desc* descs,
+                            const rgbac_image_desc* settled, const int32_t* modes, int ngroups,
+                            const rgbac_alpha_group* groups, const int32_t* block_base,
+                            int total_blocks, uint32_t* cls, int32_t* err, void* stream);
+int rgbac_color_near_tables(int batch, const rgbac_image_desc* descs, const int32_t* modes,
+                            const int32_t* block_base, int total_blocks, const uint32_t* cls,
+                            uint32_t* partials, int32_t* freqs, uint16_t* tables, void* stream);
+int rgbac_color_near_sizes(int batch, const rgbac_image_desc* descs, const int32_t* modes,
+                           int ngroups, const rgbac_alpha_group* groups,
+                           const int32_t* block_base, int total_blocks, const uint32_t* cls,
+                           const uint16_t* tables, int32_t* counts, int32_t* err, void* stream);
+int rgbac_color_near_encode(int batch, const rgbac_image_desc* descs, const int32_t* modes,
+                            int ngroups, const rgbac_alpha_group* groups,
+                            const int32_t* block_base, int total_blocks, const uint32_t* cls,
+                            const uint16_t* tables, const int32_t* counts, const int64_t* ends,
+                            uint32_t* payload, int64_t payload_words, int32_t* err, void* stream);
+int rgbac_color_near_decode(int batch, const rgbac_image_desc* descs, const int32_t* modes,
+                            int ngroups, const rgbac_alpha_group* groups,
+                            const int32_t* block_base, int total_blocks, const uint32_t* cls,
+                            const uint16_t* tables, const int64_t* word_off,
+                            const int32_t* counts, const uint32_t* payload,
+                            int64_t payload_words, int32_t* err, void* stream);
+
 /* Lane-interleaved rANS coder (csrc/rans_lanes.hip over csrc/rans_lanes.h, DESIGN.md section
  * 25): the "lanes" stream format of compress / decompress (coder="lanes").  The symbol sequence
  * is cut into groups of at most W * K symbols (W in {8, 16, 32, 64} lanes, K steps); symbol j of
