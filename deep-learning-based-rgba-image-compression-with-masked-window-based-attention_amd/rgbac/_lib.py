@@ -120,8 +120,8 @@ OPAQUE_BLOCKS = 32                              # RGBAC_OPAQUE_BLOCKS
 ALPHA_BLOCK, ALPHA_GROUP, ALPHA_CONTEXTS, ALPHA_HIST_BLOCKS, ALPHA_TABLE_U16 = 16, 64, 5, 16, 1288
 # RGBAC_COLOR_CHANNELS, _HIST_BLOCKS, _TABLE_U16
 COLOR_CHANNELS, COLOR_HIST_BLOCKS, COLOR_TABLE_U16 = 3, 16, 3856
-# RGBAC_NEAR_MAX_ERROR, _KEEP_HIDDEN
-NEAR_MAX_ERROR, NEAR_KEEP_HIDDEN = 16, 256
+# RGBAC_NEAR_MAX_ERROR, _KEEP_HIDDEN, RGBAC_BLEND_COMPOSITE
+NEAR_MAX_ERROR, NEAR_KEEP_HIDDEN, BLEND_COMPOSITE = 16, 256, 512
 
 _VP, _I32, _I64, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 _D = ctypes.c_double
@@ -316,6 +316,14 @@ SIGNATURES = {
                                 _I64, _VP, _VP],
     "rgbac_color_near_decode": [_I32, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP,
                                 _I64, _VP, _VP],
+    # the same under the composite bound (csrc/color_blend.hip)
+    "rgbac_color_blend_settle": [_I32, _VP, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP],
+    "rgbac_color_blend_tables": [_I32, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP],
+    "rgbac_color_blend_sizes": [_I32, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP],
+    "rgbac_color_blend_encode": [_I32, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP,
+                                 _I64, _VP, _VP],
+    "rgbac_color_blend_decode": [_I32, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP,
+                                 _I64, _VP, _VP],
 }
 _RESTYPE = {"rgbac_last_error": ctypes.c_char_p, "rgbac_rans_encoder_bound": ctypes.c_int64,
             "rgbac_winattn_block_workspace": ctypes.c_int64,

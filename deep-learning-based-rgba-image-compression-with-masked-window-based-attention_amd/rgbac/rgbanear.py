@@ -15,8 +15,15 @@ with step 2 delta + 1; 15 static tables per image (channel * 5 + context); one r
 block and channel that is not constant within 2 delta.  Model, format and launches: DESIGN.md
 section 28.
 
+``bound="composite"`` (csrc/color_blend.hip) bounds what people see, not the
+stored byte: the composite of every pixel over ANY background comes back within +-delta.  A pixel
+of alpha a may then be off by e(a) = min(255, 255 delta // a), which is delta where a = 255 and
+grows as the pixel fades: soft edges, shadows and glass cost fewer bytes.  Such a file has version
+2 and flags bit 1; ``keep_hidden`` has no meaning under it.
+
 File, little-endian:
-    "RGAN", u16 version (1), u16 flags (bit 0: keep_hidden), u8 delta, 3 zero bytes, u32 h, u32 w,
+    "RGAN", u16 version (1; 2 under the composite bound), u16 flags (bit 0: keep_hidden, bit 1:
+    composite bound, version 2 only and never with bit 0), u8 delta, 3 zero bytes, u32 h, u32 w,
     u32 alpha bytes, u32 colour bytes; the RGAP blob; the colour section in the layout of an RGAL
     file's (rgbac.rgbalossless): u32 chunks, u32 payload words, 15 tables, one u32 class word per
     block (bit 0 hidden, bits 1-3 channel G / R / B constant, bits 8-15 / 16-23 / 24-31 the
@@ -34,6 +41,9 @@ from .ans import _raise_code, _upload
 
 MAGIC = b"RGAN"
 VERSION = 1
+VERSION_COMPOSITE = 2                 # the bound is on the composite: flags bit 1, never bit 0
+FLAG_COMPOSITE = 2
+BOUNDS = ("pixel", "composite")
 MAX_ERROR = _lib.NEAR_MAX_ERROR
 NCH, NCTX, NTAB = rl.NCH, rl.NCTX, rl.NTAB
 _HEADER = struct.Struct("<4sHHB3sIIII")
@@ -50,21 +60,43 @@ def _delta(max_error, who):
     return int(max_error)
 
 
+def _composite(bound, keep_hidden, who):
+    """Is ``bound`` the composite bound?"""
+    if bound not in BOUNDS:
+        raise ValueError(f"{who}: bound must be one of {BOUNDS}, got {bound!r}")
+    if bound == "composite" and keep_hidden:
+        raise ValueError(f"{who}: keep_hidden has no meaning under bound='composite' (a hidden "
+                         "pixel adds nothing to any composite)")
+    return bound == "composite"
+
+
 def max_quantised(delta):
-    """The largest |q| a file of this delta can hold."""
+    """The largest |q| a file of this delta can hold (a tolerance e >= delta only lowers it)."""
     return (255 + delta) // (2 * delta + 1)
 
 
-def build_rgba_near(h, w, delta, keep_hidden, alpha, colour):
-    return _HEADER.pack(MAGIC, VERSION, rl.FLAG_KEEP_HIDDEN if keep_hidden else 0, delta,
+def tolerance(alpha, delta, composite):
+    """Per-pixel tolerance e of the colour bytes: delta, or under the composite bound
+    min(255, 255 delta // a) (255 where a = 0: such a pixel is hidden and never coded)."""
+    a = np.asarray(alpha).astype(np.int64)
+    if not composite:
+        return np.full(a.shape, delta, dtype=np.int64)
+    return np.where(a > 0, np.minimum(255, 255 * delta // np.maximum(a, 1)), 255)
+
+
+def build_rgba_near(h, w, delta, keep_hidden, alpha, colour, composite=False):
+    flags = (rl.FLAG_KEEP_HIDDEN if keep_hidden else 0) | (FLAG_COMPOSITE if composite else 0)
+    return _HEADER.pack(MAGIC, VERSION_COMPOSITE if composite else VERSION, flags, delta,
                         b"\0\0\0", h, w, len(alpha), len(colour)) + alpha + colour
 
 
 def parse_rgba_near(blob):
-    """bytes -> parse_rgba_lossless's dictionary plus "delta".  Pure host code; raises
-    RuntimeError on anything wrong.  After its own header (magic, version, delta in 1..16, zero
-    reserved bytes) an RGAN file is laid out as an RGAL file, so the rest is parse_rgba_lossless's
-    work and every one of its rejections holds here.  On top of them: no table may give a
+    """bytes -> parse_rgba_lossless's dictionary plus "delta" and "bound" ("pixel" or
+    "composite").  Pure host code; raises RuntimeError on anything wrong.  After its own header
+    (magic, version 1 or 2, delta in 1..16, zero reserved bytes; flags bit 1, the composite bound,
+    set in a version 2 file, where bit 0 must be clear, and in no other) an RGAN file is laid out
+    as an RGAL file, so the rest is parse_rgba_lossless's work and every one of its rejections
+    holds here.  On top of them: no table may give a
     frequency to a symbol whose |q| exceeds (255 + delta) div (2 delta + 1) -- except the
     companion symbol of frequency 1 that the table rule adds to a one-symbol context, which no
     stream ever codes."""
@@ -78,8 +110,15 @@ def parse_rgba_near(blob):
     magic, version, flags, delta, reserved, h, w, alpha_len, colour_len = _HEADER.unpack_from(blob)
     if magic != MAGIC:
         raise bad("bad magic (not an RGAN file)")
-    if version != VERSION:
+    if version not in (VERSION, VERSION_COMPOSITE):
         raise bad(f"unsupported version {version}")
+    composite = version == VERSION_COMPOSITE
+    if bool(flags & FLAG_COMPOSITE) != composite:
+        raise bad(f"flags {flags:#x} do not fit version {version} (bit 1, the composite bound, "
+                  "belongs to version 2 alone)")
+    if composite and flags & rl.FLAG_KEEP_HIDDEN:
+        raise bad("keep_hidden under the composite bound")
+    flags &= ~FLAG_COMPOSITE
     if not 1 <= delta <= MAX_ERROR:
         raise bad(f"max_error {delta} is outside 1..{MAX_ERROR}")
     if reserved != b"\0\0\0":
@@ -98,6 +137,7 @@ def parse_rgba_near(blob):
         if outside[nz].any():
             raise bad(f"table {c} has a symbol outside the range of max_error {delta}")
     f["delta"] = delta
+    f["bound"] = BOUNDS[composite]
     return f
 
 
@@ -115,10 +155,12 @@ def _model(eL, eU, eD, L, U, D):
     return np.where(both, med, np.where(some, one, 0)), np.where(both, bins, np.where(some, 0, 4))
 
 
-def settle_host(image, delta, keep_hidden=False):
+def settle_host(image, delta, keep_hidden=False, bound="pixel"):
     """(h, w, 4) uint8 -> (recon (h, w, 4) uint8, class words (blocks,) uint32, symbols
     (blocks, 3, 16, 16), contexts likewise, visible (blocks, 16, 16)): the model of DESIGN.md
-    section 28.  Symbols of hidden pixels and of constant channels mean nothing."""
+    section 28, and of section 29 for ``bound="composite"`` (with every tolerance equal to delta
+    the two are one).  Symbols of hidden pixels and of constant channels mean nothing."""
+    composite = _composite(bound, keep_hidden, "settle_host")
     a = np.asarray(image).astype(np.int64)
     h, w = a.shape[:2]
     by, bx = -(-h // BLOCK), -(-w // BLOCK)
@@ -133,12 +175,12 @@ def settle_host(image, delta, keep_hidden=False):
 
     V = blocks(inside & (True if keep_hidden else pad[..., 3] != 0))
     S = blocks(pad[..., [1, 0, 2]])                       # G, R, B
-    step = 2 * delta + 1
-    small = np.where(V[..., None], S, 256).min(axis=(1, 2))
-    big = np.where(V[..., None], S, -1).max(axis=(1, 2))
+    E = blocks(tolerance(pad[..., 3], delta, composite))  # per pixel; the step is 2 E + 1
+    lo = np.where(V[..., None], S - E[..., None], -512).max(axis=(1, 2))
+    hi = np.where(V[..., None], S + E[..., None], 512).min(axis=(1, 2))
     seen = V.any(axis=(1, 2))
-    const = seen[:, None] & (big - small <= 2 * delta)
-    value = (small + big) >> 1
+    const = seen[:, None] & (lo <= hi)                    # at E = delta: max - min <= 2 delta
+    value = np.clip((lo + hi) >> 1, 0, 255)               # at E = delta: (min + max) >> 1
     cls = np.where(seen, (const * (2 << np.arange(NCH))).sum(axis=1)
                    + (const * value << (8 + 8 * np.arange(NCH))).sum(axis=1), _HIDDEN)
     rec = np.zeros_like(S)
@@ -155,8 +197,8 @@ def settle_host(image, delta, keep_hidden=False):
                     return rec[:, rr, cc, ch] - (rec[:, rr, cc, 0] if ch else 0)
                 p, k = _model(eL, eU, eD, plane(r, c - 1), plane(r - 1, c), plane(r - 1, c - 1))
                 P = np.clip(rec[:, r, c, 0] + p, 0, 255) if ch else p
-                e = S[:, r, c, ch] - P
-                q = np.sign(e) * ((np.abs(e) + delta) // step)
+                e, step = S[:, r, c, ch] - P, 2 * E[:, r, c] + 1
+                q = np.sign(e) * ((np.abs(e) + E[:, r, c]) // step)
                 rec[:, r, c, ch] = np.where(const[:, ch], value[:, ch],
                                             np.clip(P + q * step, 0, 255))
                 sym[:, ch, r, c], ctx[:, ch, r, c] = q & 255, k
@@ -167,16 +209,17 @@ def settle_host(image, delta, keep_hidden=False):
     return recon, cls.astype(np.uint32), sym, ctx, V
 
 
-def encode_rgba_near_host(image, max_error, keep_hidden=False):
+def encode_rgba_near_host(image, max_error, keep_hidden=False, bound="pixel"):
     """encode_rgba_near for one image on the CPU -> (bytes, the decoded image as (h, w, 4) uint8):
     the kernels' byte-level reference (not a fallback; the device path never calls it)."""
     from .ans import encode_table_host
     delta = _delta(max_error, "encode_rgba_near_host")
+    composite = _composite(bound, keep_hidden, "encode_rgba_near_host")
     a = np.ascontiguousarray(np.asarray(image, dtype=np.uint8))
     if a.ndim != 3 or a.shape[2] != 4 or a.size == 0 or max(a.shape[:2]) > MAX_SIDE:
         raise ValueError(f"encode_rgba_near_host: expected (H, W, 4) uint8 RGBA, got {a.shape}")
     h, w = a.shape[:2]
-    recon, cls, sym, ctx, V = settle_host(a, delta, keep_hidden)
+    recon, cls, sym, ctx, V = settle_host(a, delta, keep_hidden, bound)
     has = rl._chunk_mask(cls)
     s = [sym[k, ch][V[k]] for k, ch in zip(*np.nonzero(has))]           # raster order
     t = [ctx[k, ch][V[k]] + NCTX * ch for k, ch in zip(*np.nonzero(has))]
@@ -193,26 +236,31 @@ def encode_rgba_near_host(image, max_error, keep_hidden=False):
         counts, payload = words[:lens.size], words[lens.size:].view(np.uint32)
     blob = build_rgba_near(h, w, delta, keep_hidden,
                            alphaexact.encode_alpha_plane_host(a[..., 3]),
-                           rl.build_colour(freqs, cls, counts, payload))
+                           rl.build_colour(freqs, cls, counts, payload), composite)
     return blob, recon
 
 
 # ---- launches
-def _modes(deltas, keeps, dev):
-    """The kernels' per-image mode words: delta, bit 8 keep_hidden."""
+def _modes(deltas, keeps, composites, dev):
+    """The kernels' per-image mode words: delta, bit 8 keep_hidden, bit 9 the composite bound
+    (csrc/color_blend.hip alone knows that bit)."""
     return _upload(np.asarray([d | (_lib.NEAR_KEEP_HIDDEN if k else 0)
-                               for d, k in zip(deltas, keeps)], dtype=np.int32), dev)
+                               | (_lib.BLEND_COMPOSITE if c else 0)
+                               for d, k, c in zip(deltas, keeps, composites)], dtype=np.int32), dev)
 
 
 def _args(wk, descs, modes, grouped):
-    """The leading arguments of the rgbac_color_near_* calls from alphaexact's geometry."""
+    """The leading arguments of the rgbac_color_near_* and rgbac_color_blend_* calls from
+    alphaexact's geometry."""
     mid = (wk.ngroups, wk._groups.data_ptr()) if grouped else ()
     return (wk.B, descs.data_ptr(), modes.data_ptr()) + mid + (wk._base.data_ptr(), wk.N)
 
 
-def _encode_colour(dev, sizes, entries, delta, keep_hidden):
+def _encode_colour(dev, sizes, entries, delta, keep_hidden, composite):
     """The six launches over a ragged batch (settle, histogram, normalise, sizes, encode) and
-    the two host reads -> (one colour section per image, the settled images)."""
+    the two host reads -> (one colour section per image, the settled images).  ``composite``
+    takes them through csrc/color_blend.hip, otherwise they are csrc/color_near.hip's."""
+    fn = "rgbac_color_blend_" if composite else "rgbac_color_near_"
     wk = alphaexact._Work(sizes, entries, 4, dev)
     B, N, nf = wk.B, wk.N, NTAB * 256
     cut_px = np.concatenate([[0], np.cumsum([h * w for h, w in sizes])])
@@ -221,18 +269,18 @@ def _encode_colour(dev, sizes, entries, delta, keep_hidden):
              for i, (h, w) in enumerate(sizes)]
     settled = anysize._upload_descs([(t.data_ptr(), h, w, 4 * w)
                                      for t, (h, w) in zip(recon, sizes)], dev)
-    modes = _modes([delta] * B, [keep_hidden] * B, dev)
+    modes = _modes([delta] * B, [keep_hidden] * B, [composite] * B, dev)
     meta = torch.empty((1 + NCH) * N + B * nf, dtype=torch.int32, device=dev)
     cls, counts, freqs = meta[:N], meta[N:(1 + NCH) * N], meta[(1 + NCH) * N:]
     partials = torch.empty(B * _lib.COLOR_HIST_BLOCKS * nf, dtype=torch.int32, device=dev)
     tables = torch.empty(B * _lib.COLOR_TABLE_U16, dtype=torch.int16, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     plain, grouped = _args(wk, settled, modes, False), _args(wk, settled, modes, True)
-    _lib.call("rgbac_color_near_settle", B, wk._descs.data_ptr(), *grouped[1:], cls.data_ptr(),
+    _lib.call(fn + "settle", B, wk._descs.data_ptr(), *grouped[1:], cls.data_ptr(),
               err.data_ptr(), wk.stream)
-    _lib.call("rgbac_color_near_tables", *plain, cls.data_ptr(), partials.data_ptr(),
+    _lib.call(fn + "tables", *plain, cls.data_ptr(), partials.data_ptr(),
               freqs.data_ptr(), tables.data_ptr(), wk.stream)
-    _lib.call("rgbac_color_near_sizes", *grouped, cls.data_ptr(), tables.data_ptr(),
+    _lib.call(fn + "sizes", *grouped, cls.data_ptr(), tables.data_ptr(),
               counts.data_ptr(), err.data_ptr(), wk.stream)
     ends = torch.cumsum(counts, 0, dtype=torch.int64)
     host = meta.cpu().numpy()                                       # the sizes: one read
@@ -243,7 +291,7 @@ def _encode_colour(dev, sizes, entries, delta, keep_hidden):
     total = int(cut[-1])
     words = torch.empty(total + 1, dtype=torch.int32, device=dev)
     if total:
-        _lib.call("rgbac_color_near_encode", *grouped, cls.data_ptr(), tables.data_ptr(),
+        _lib.call(fn + "encode", *grouped, cls.data_ptr(), tables.data_ptr(),
                   counts.data_ptr(), ends.data_ptr(), words.data_ptr(), total, err.data_ptr(),
                   wk.stream)
     words[total:].copy_(err)
@@ -258,15 +306,20 @@ def _encode_colour(dev, sizes, entries, delta, keep_hidden):
     return out, recon
 
 
-def encode_rgba_near(images, max_error, keep_hidden=False, return_recon=False, device="cuda"):
+def encode_rgba_near(images, max_error, keep_hidden=False, return_recon=False, device="cuda",
+                     bound="pixel"):
     """images: a list of (h, w, 4) uint8 RGBA images of any sizes; GPU tensors are read in place,
     views into larger buffers included -> list[bytes], one RGAN file per image; with
     ``return_recon`` also the list of decoded images, (h, w, 4) uint8 GPU tensors (the encoder
     builds them before it can form a symbol).  ``max_error``: an int delta in 1..16, the bound on
     every colour byte of a visible pixel.  A hidden pixel (alpha 0) decodes to R = G = B = 0 and
-    its colour does not reach the file; ``keep_hidden`` codes every pixel's colour.  A file does
-    not depend on the images coded with it."""
+    its colour does not reach the file; ``keep_hidden`` codes every pixel's colour.
+    ``bound="composite"`` bounds the composite (a C + (255 - a) B) / 255 over any background B by
+    ``max_error`` instead of the colour byte: a pixel of alpha a may be off by
+    min(255, 255 max_error // a).  It writes version 2 files and excludes ``keep_hidden``.  A
+    file does not depend on the images coded with it."""
     delta = _delta(max_error, "encode_rgba_near")
+    composite = _composite(bound, keep_hidden, "encode_rgba_near")
     dev = anysize._gpu_device(device)
     _lib.load()
     dev, sizes, entries, keep = anysize._sources(images, dev, "encode_rgba_near")
@@ -274,15 +327,17 @@ def encode_rgba_near(images, max_error, keep_hidden=False, return_recon=False, d
         raise ValueError(f"encode_rgba_near: an image side is at most {MAX_SIDE}")
     keep_hidden = bool(keep_hidden)
     alpha = alphaexact._encode(dev, sizes, rl._alpha_entries(entries), 4)
-    colour, recon = _encode_colour(dev, sizes, entries, delta, keep_hidden)
-    blobs = [build_rgba_near(h, w, delta, keep_hidden, a, c)
+    colour, recon = _encode_colour(dev, sizes, entries, delta, keep_hidden, composite)
+    blobs = [build_rgba_near(h, w, delta, keep_hidden, a, c, composite)
              for (h, w), a, c in zip(sizes, alpha, colour)]
     return (blobs, recon) if return_recon else blobs
 
 
 def decode_rgba_near(blobs, device="cuda"):
-    """blobs: files from encode_rgba_near, any number, any order, any mix of max_error and
-    keep_hidden -> list of (h, w, 4) uint8 GPU tensors in the same order.  Every file is parsed
+    """blobs: files from encode_rgba_near, any number, any order, any mix of max_error,
+    keep_hidden and bound -> list of (h, w, 4) uint8 GPU tensors in the same order.  A list with
+    a composite-bound file in it goes through csrc/color_blend.hip as a whole (its other files
+    get a flat tolerance table there), any other list through csrc/color_near.hip.  Every file is parsed
     and validated on the host before any launch (RuntimeError); one plane-decoder launch puts all
     alpha planes into the outputs' alpha bytes, one colour launch fills in R, G, B on the same
     stream; the one error word is read once at the end."""
@@ -298,7 +353,9 @@ def decode_rgba_near(blobs, device="cuda"):
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     alphaexact._decode([f["alpha"] for f in parsed], rl._alpha_entries(entries), 4, dev, err)
     wk = alphaexact._Work([(f["h"], f["w"]) for f in parsed], entries, 4, dev)
-    modes = _modes([f["delta"] for f in parsed], [f["keep_hidden"] for f in parsed], dev)
+    composite = [f["bound"] == "composite" for f in parsed]
+    modes = _modes([f["delta"] for f in parsed], [f["keep_hidden"] for f in parsed], composite,
+                   dev)
     counts = np.concatenate([f["counts"].reshape(-1) for f in parsed])
     pbase = np.concatenate([[0], np.cumsum([f["payload"].size for f in parsed])])
     off = np.concatenate([pbase[i] + np.cumsum(f["counts"].reshape(-1), dtype=np.int64)
@@ -311,8 +368,8 @@ def decode_rgba_near(blobs, device="cuda"):
     tables = _upload(np.concatenate([rl.device_table(f["freqs"]) for f in parsed])
                      .view(np.int16), dev)
     N = wk.N
-    _lib.call("rgbac_color_near_decode", *_args(wk, wk._descs, modes, True), ints[:N].data_ptr(),
-              tables.data_ptr(), off.data_ptr(), ints[N:(1 + NCH) * N].data_ptr(),
+    _lib.call("rgbac_color_blend_decode" if any(composite) else "rgbac_color_near_decode",
+              *_args(wk, wk._descs, modes, True), ints[:N].data_ptr(), tables.data_ptr(), off.data_ptr(), ints[N:(1 + NCH) * N].data_ptr(),
               ints[(1 + NCH) * N:].data_ptr(), int(pbase[-1]), err.data_ptr(), wk.stream)
     _raise_code("RGAN file decode", int(err.item()))
     return outs

@@ -1166,6 +1166,47 @@ int rgbac_color_near_decode(int batch, const rgbac_image_desc* descs, const int3
                             const int32_t* counts, const uint32_t* payload,
                             int64_t payload_words, int32_t* err, void* stream);
 
+/* Composite-bounded near-lossless colour of packed RGBA (csrc/color_blend.hip, rgbac/rgbanear.py,
+ * DESIGN.md section 29): rgbac_color_near_*'s coder with a tolerance that follows the pixel's
+ * alpha, so that the composite over any background stays within +-delta.  The argument lists,
+ * arrays, error codes and launches are those of the rgbac_color_near_* counterparts.
+ *   modes: as above, plus bit 9 (RGBAC_BLEND_COMPOSITE): the composite bound.  A pixel of alpha
+ *     a in 1..255 may then be off by e(a) = min(255, (255 delta) div a); its quantiser has step
+ *     2 e(a) + 1, and a channel is constant in a block iff max(C_i - e_i) <= min(C_i + e_i) over
+ *     the block's visible pixels, at the clamped midpoint.  Bits 8 and 9 together, or any other
+ *     bit, make the image's groups report code 5 and touch nothing.  With bit 9 clear every entry
+ *     point computes exactly what its rgbac_color_near_* counterpart computes, so one decode
+ *     launch serves files of both bounds.
+ * Every workgroup builds a 256-entry LDS table alpha -> (e, ceil(2^18 / step)) from its image's
+ * mode word; no kernel divides integers.
+ * rgbac_color_blend_settle: the 31-step wavefront of a block runs in the registers of 16 lanes
+ *   (one shuffle per step, no barrier between the steps).
+ * rgbac_color_blend_decode: code 3 (corrupt) also for a symbol whose |q| exceeds
+ *   (255 + e) div (2 e + 1) at its pixel; the destinations' alpha bytes must be in place. */
+#define RGBAC_BLEND_COMPOSITE 512
+int rgbac_color_blend_settle(int batch, const rgbac_image_desc* descs,
+                             const rgbac_image_desc* settled, const int32_t* modes, int ngroups,
+                             const rgbac_alpha_group* groups, const int32_t* block_base,
+                             int total_blocks, uint32_t* cls, int32_t* err, void* stream);
+int rgbac_color_blend_tables(int batch, const rgbac_image_desc* descs, const int32_t* modes,
+                             const int32_t* block_base, int total_blocks, const uint32_t* cls,
+                             uint32_t* partials, int32_t* freqs, uint16_t* tables, void* stream);
+int rgbac_color_blend_sizes(int batch, const rgbac_image_desc* descs, const int32_t* modes,
+                            int ngroups, const rgbac_alpha_group* groups,
+                            const int32_t* block_base, int total_blocks, const uint32_t* cls,
+                            const uint16_t* tables, int32_t* counts, int32_t* err, void* stream);
+int rgbac_color_blend_encode(int batch, const rgbac_image_desc* descs, const int32_t* modes,
+                             int ngroups, const rgbac_alpha_group* groups,
+                             const int32_t* block_base, int total_blocks, const uint32_t* cls,
+                             const uint16_t* tables, const int32_t* counts, const int64_t* ends,
+                             uint32_t* payload, int64_t payload_words, int32_t* err, void* stream);
+int rgbac_color_blend_decode(int batch, const rgbac_image_desc* descs, const int32_t* modes,
+                             int ngroups, const rgbac_alpha_group* groups,
+                             const int32_t* block_base, int total_blocks, const uint32_t* cls,
+                             const uint16_t* tables, const int64_t* word_off,
+                             const int32_t* counts, const uint32_t* payload,
+                             int64_t payload_words, int32_t* err, void* stream);
+
 /* Lane-interleaved rANS coder (csrc/rans_lanes.hip over csrc/rans_lanes.h, DESIGN.md section
  * 25): the "lanes" stream format of compress / decompress (coder="lanes").  The symbol sequence
  * is cut into groups of at most W * K symbols (W in {8, 16, 32, 64} lanes, K steps); symbol j of
