@@ -120,6 +120,8 @@ OPAQUE_BLOCKS = 32                              # RGBAC_OPAQUE_BLOCKS
 ALPHA_BLOCK, ALPHA_GROUP, ALPHA_CONTEXTS, ALPHA_HIST_BLOCKS, ALPHA_TABLE_U16 = 16, 64, 5, 16, 1288
 # RGBAC_COLOR_CHANNELS, _HIST_BLOCKS, _TABLE_U16
 COLOR_CHANNELS, COLOR_HIST_BLOCKS, COLOR_TABLE_U16 = 3, 16, 3856
+# RGBAC_COLOR_ADAPT_KINDS, _TABLE_U16
+COLOR_ADAPT_KINDS, COLOR_ADAPT_TABLE_U16 = 5, 6426
 # RGBAC_NEAR_MAX_ERROR, _KEEP_HIDDEN, RGBAC_BLEND_COMPOSITE
 NEAR_MAX_ERROR, NEAR_KEEP_HIDDEN, BLEND_COMPOSITE = 16, 256, 512
 
@@ -307,6 +309,14 @@ SIGNATURES = {
     "rgbac_color_exact_encode": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP,
                                  _I64, _VP, _VP],
     "rgbac_color_exact_decode": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP,
+                                 _I64, _VP, _VP],
+    # the same with the colour transform chosen per block (csrc/color_adapt.hip)
+    "rgbac_color_adapt_choose": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP],
+    "rgbac_color_adapt_tables": [_I32, _VP, _I32, _VP, _I32, _VP, _VP, _VP, _VP, _VP],
+    "rgbac_color_adapt_sizes": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP],
+    "rgbac_color_adapt_encode": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP,
+                                 _I64, _VP, _VP],
+    "rgbac_color_adapt_decode": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP,
                                  _I64, _VP, _VP],
     # near-lossless colour of packed RGBA (csrc/color_near.hip)
     "rgbac_color_near_settle": [_I32, _VP, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP],

@@ -12,12 +12,20 @@ MED prediction inside 16 x 16 blocks over the neighbours that are visible, 15 st
 image (channel * 5 + context), one rANS chunk per block and channel that is not constant.  Model,
 format and launches: DESIGN.md section 26.
 
+``transform="adaptive"`` (csrc/color_adapt.hip) lets every block choose, for
+red and for blue on their own, between the difference from green and the plain channel, whichever
+the model codes in fewer bits: five planes Y, Cr, Cb, R, B with 25 tables (kind * 5 + context),
+class word bit 4 / 5 = the red / blue slot holds the plain channel.  Such files are version 2;
+``transform="green"``, the default, writes what it always wrote.
+
 File, little-endian:
-    "RGAL", u16 version (1), u16 flags (bit 0: keep_hidden), u32 h, u32 w, u32 alpha bytes, u32
-    colour bytes; the RGAP blob; the colour section: u32 chunks, u32 payload words; 15 tables in
-    the RGAP table form, channel-major; one u32 class word per block, row-major (bit 0 hidden,
-    bits 1-3 channel Y / Cr / Cb constant, bits 8-15 / 16-23 / 24-31 the constants); one u16 word
-    count per chunk (block-major, Y, Cr, Cb); the payload, u32 words.
+    "RGAL", u16 version (1; 2 adaptive), u16 flags (bit 0: keep_hidden; bit 1: adaptive, set in
+    every version 2 file and in no other), u32 h, u32 w, u32 alpha bytes, u32 colour bytes; the
+    RGAP blob; the colour section: u32 chunks, u32 payload words; 15 tables (25 in version 2) in
+    the RGAP table form, channel-major (kind-major); one u32 class word per block, row-major (bit
+    0 hidden, bits 1-3 channel Y / Cr / Cb constant, version 2: bits 4 / 5 plain R / B, bits
+    8-15 / 16-23 / 24-31 the constants); one u16 word count per chunk (block-major, Y, Cr, Cb);
+    the payload, u32 words.
 """
 import struct
 
@@ -30,10 +38,16 @@ from .ans import _raise_code, _upload
 
 MAGIC = b"RGAL"
 VERSION = 1
+VERSION_ADAPTIVE = 2
 FLAG_KEEP_HIDDEN = 1
+FLAG_ADAPTIVE = 2
+TRANSFORMS = ("green", "adaptive")    # by version - 1
 NCH = _lib.COLOR_CHANNELS
 NCTX = alphaexact.NCTX
 NTAB = NCH * NCTX                     # 15 tables: channel * 5 + context
+NKIND = _lib.COLOR_ADAPT_KINDS        # adaptive: the planes Y, Cr, Cb, R, B
+NTAB_ADAPTIVE = NKIND * NCTX          # 25 tables: kind * 5 + context
+PLAIN_R, PLAIN_B = 16, 32             # class word, adaptive: the red / blue slot holds R / B
 _HEADER = struct.Struct("<4sHHIIII")
 HEADER_BYTES = _HEADER.size           # 24
 _HIDDEN = 1                           # the class word of a block without a visible pixel
@@ -47,29 +61,32 @@ def _chunk_mask(cls):
 
 def device_table(freqs):
     """(15, 256) frequencies -> the uint16[3856] table the kernels stage in LDS: exclusive sums
-    mod 2^16, the last symbol with a frequency per table (-1: empty), one zero."""
-    f = np.asarray(freqs, dtype=np.int64).reshape(NTAB, 256)
-    tab = np.zeros(_lib.COLOR_TABLE_U16, dtype=np.uint16)
-    tab[:NTAB * 256] = ((np.cumsum(f, axis=1) - f) & 0xFFFF).reshape(-1)
-    for c in range(NTAB):
+    mod 2^16, the last symbol with a frequency per table (-1: empty), one zero.  (25, 256), the
+    adaptive transform's, -> uint16[6426] in the same form."""
+    f = np.asarray(freqs, dtype=np.int64).reshape(-1, 256)
+    ntab = f.shape[0]
+    tab = np.zeros(ntab * 257 + 1, dtype=np.uint16)
+    tab[:ntab * 256] = ((np.cumsum(f, axis=1) - f) & 0xFFFF).reshape(-1)
+    for c in range(ntab):
         nz = np.flatnonzero(f[c])
-        tab[NTAB * 256 + c] = np.int16(nz[-1] if nz.size else -1).view(np.uint16)
+        tab[ntab * 256 + c] = np.int16(nz[-1] if nz.size else -1).view(np.uint16)
     return tab
 
 
 def host_tables(freqs):
-    """(15, 256) frequencies -> the rgbac.ans.CdfTables the host chunk coder takes (rows of 258
-    entries, as alphaexact.host_tables)."""
+    """(15, 256) or (25, 256) frequencies -> the rgbac.ans.CdfTables the host chunk coder takes
+    (rows of 258 entries, as alphaexact.host_tables)."""
     from .ans import CdfTables
-    f = np.asarray(freqs, dtype=np.int64).reshape(NTAB, 256)
-    cdfs = np.zeros((NTAB, 258), dtype=np.int32)
+    f = np.asarray(freqs, dtype=np.int64).reshape(-1, 256)
+    ntab = f.shape[0]
+    cdfs = np.zeros((ntab, 258), dtype=np.int32)
     cdfs[:, 1:257] = np.cumsum(f, axis=1)
     cdfs[:, 257] = cdfs[:, 256]
-    return CdfTables(cdfs, [258] * NTAB, [0] * NTAB)
+    return CdfTables(cdfs, [258] * ntab, [0] * ntab)
 
 
 def build_colour(freqs, cls, counts, payload):
-    """The pieces of one image's colour section -> bytes.  freqs (15, 256); cls: the blocks'
+    """The pieces of one image's colour section -> bytes.  freqs (15 or 25, 256); cls: the blocks'
     class words; counts: the chunks' word counts in chunk order; payload: their words."""
     counts = np.asarray(counts)
     return b"".join(
@@ -79,16 +96,26 @@ def build_colour(freqs, cls, counts, payload):
            np.asarray(payload).astype("<u4").tobytes()])
 
 
-def build_rgba_lossless(h, w, keep_hidden, alpha, colour):
-    return _HEADER.pack(MAGIC, VERSION, FLAG_KEEP_HIDDEN if keep_hidden else 0, h, w, len(alpha),
-                        len(colour)) + alpha + colour
+def build_rgba_lossless(h, w, keep_hidden, alpha, colour, adaptive=False):
+    flags = (FLAG_KEEP_HIDDEN if keep_hidden else 0) | (FLAG_ADAPTIVE if adaptive else 0)
+    return _HEADER.pack(MAGIC, VERSION_ADAPTIVE if adaptive else VERSION, flags, h, w,
+                        len(alpha), len(colour)) + alpha + colour
+
+
+def _adaptive(transform, who):
+    if transform not in TRANSFORMS:
+        raise ValueError(f"{who}: transform must be one of {TRANSFORMS}, got {transform!r}")
+    return transform == "adaptive"
 
 
 def parse_rgba_lossless(blob):
-    """bytes -> {"h", "w", "keep_hidden", "alpha": the parsed RGAP blob, "freqs" (15, 256) int64,
-    "cls" uint32 per block, "counts" int32 (blocks, 3) (0 where there is no chunk), "payload"
+    """bytes -> {"h", "w", "keep_hidden", "transform" ("green": version 1, "adaptive": version
+    2), "alpha": the parsed RGAP blob, "freqs" (15, 256) int64, (25, 256) if adaptive, "cls"
+    uint32 per block, "counts" int32 (blocks, 3) (0 where there is no chunk), "payload"
     uint32}.  Pure host code; raises RuntimeError on anything wrong: bad magic, version, flags or
-    size; truncation or over-length; section lengths that disagree; an alpha blob that
+    size (flags bit 1 belongs to version 2, which always has it; class bits 4 and 5 to version 2,
+    bits 6 and 7 to none); truncation or over-length; section lengths that disagree; an alpha
+    blob that
     parse_alpha_planes rejects or of another size; tables that are not fixed points of
     normalise_counts; class words with reserved bits set, a hidden word that is not 1 or a value
     byte under a clear flag; a chunk table whose length is not what the class words imply; word
@@ -103,10 +130,15 @@ def parse_rgba_lossless(blob):
     magic, version, flags, h, w, alpha_len, colour_len = _HEADER.unpack_from(blob)
     if magic != MAGIC:
         raise bad("bad magic (not an RGAL file)")
-    if version != VERSION:
+    if version not in (VERSION, VERSION_ADAPTIVE):
         raise bad(f"unsupported version {version}")
-    if flags & ~FLAG_KEEP_HIDDEN:
-        raise bad(f"unknown flags {flags:#x}")
+    adaptive = version == VERSION_ADAPTIVE
+    if adaptive and not flags & FLAG_ADAPTIVE:
+        raise bad(f"unsupported version {version} with flags {flags:#x} (a version 2 file has "
+                  "bit 1, the adaptive transform)")
+    if flags & ~(FLAG_KEEP_HIDDEN | (FLAG_ADAPTIVE if adaptive else 0)):
+        raise bad(f"unknown flags {flags:#x} in a version {version} file")
+    ntab = NTAB_ADAPTIVE if adaptive else NTAB
     if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
         raise bad(f"bad size {h}x{w}")
     total = HEADER_BYTES + alpha_len + colour_len
@@ -127,8 +159,8 @@ def parse_rgba_lossless(blob):
         return sec[pos - n:pos]
 
     nchunks, nwords = struct.unpack("<II", take(8, "header"))
-    freqs = np.zeros((NTAB, 256), dtype=np.int64)
-    for c in range(NTAB):
+    freqs = np.zeros((ntab, 256), dtype=np.int64)
+    for c in range(ntab):
         n = struct.unpack("<H", take(2, "tables"))[0]
         if n > 256 or n == 1:
             raise bad(f"table {c} lists {n} symbols")
@@ -147,7 +179,7 @@ def parse_rgba_lossless(blob):
             raise bad(f"table {c} is not a normalised table")
     npix = block_grid(h, w)[2]
     cls = np.frombuffer(take(4 * npix.size, "class table"), dtype="<u4").astype(np.uint32)
-    if (cls & 0xF0).any():
+    if (cls & (0xC0 if adaptive else 0xF0)).any():
         raise bad("class table: reserved bits set")
     if ((cls & 1) & (cls != _HIDDEN)).any():
         raise bad("class table: a hidden block's word is not 1")
@@ -170,8 +202,9 @@ def parse_rgba_lossless(blob):
         raise bad(f"the colour section is over-long: {len(sec) - pos} bytes after the payload")
     counts = np.zeros(has.shape, dtype=np.int32)
     counts[has] = cnt
-    return {"h": h, "w": w, "keep_hidden": bool(flags & FLAG_KEEP_HIDDEN), "alpha": alpha,
-            "freqs": freqs, "cls": cls, "counts": counts, "payload": payload}
+    return {"h": h, "w": w, "keep_hidden": bool(flags & FLAG_KEEP_HIDDEN),
+            "transform": TRANSFORMS[adaptive], "alpha": alpha, "freqs": freqs, "cls": cls,
+            "counts": counts, "payload": payload}
 
 
 # ---- the CPU twin: the model in numpy, the chunks by the host chunk coder (rgbac.ans)
@@ -183,15 +216,17 @@ def _shift(a, dy, dx):
     return out
 
 
-def model_symbols(image, keep_hidden=False):
+def model_symbols(image, keep_hidden=False, adaptive=False):
     """(h, w, 4) uint8 -> (symbols (3, h, w), contexts (3, h, w), visible (h, w)): the model of
     DESIGN.md section 26 for every pixel of the planes Y, Cr, Cb, each inside its own 16 x 16
-    block; entries of hidden pixels mean nothing."""
+    block; entries of hidden pixels mean nothing.  ``adaptive``: (5, h, w), the planes Y, Cr, Cb,
+    R, B of DESIGN.md section 30."""
     a = np.asarray(image).astype(np.int64)
     h, w = a.shape[:2]
     vis = np.ones((h, w), dtype=bool) if keep_hidden else a[..., 3] != 0
     g = a[..., 1]
-    v = np.stack([g, (a[..., 0] - g + 128) & 255, (a[..., 2] - g + 128) & 255])
+    v = np.stack([g, (a[..., 0] - g + 128) & 255, (a[..., 2] - g + 128) & 255]
+                 + ([a[..., 0], a[..., 2]] if adaptive else []))
     inr = np.broadcast_to((np.arange(h) % BLOCK != 0)[:, None], (h, w))
     inc = np.broadcast_to((np.arange(w) % BLOCK != 0)[None, :], (h, w))
     eL, eU, eD = _shift(vis, 0, 1) & inc, _shift(vis, 1, 0) & inr, _shift(vis, 1, 1) & inr & inc
@@ -208,17 +243,21 @@ def model_symbols(image, keep_hidden=False):
     return ((v - pred) & 255).astype(np.int32), ctx.astype(np.int32), vis
 
 
-def encode_rgba_lossless_host(image, keep_hidden=False):
+def encode_rgba_lossless_host(image, keep_hidden=False, transform="green"):
     """encode_rgba_lossless for one image on the CPU: the kernels' byte-level reference (not a
     fallback; the device path never calls it)."""
     from .ans import encode_table_host
+    adaptive = _adaptive(transform, "encode_rgba_lossless_host")
     a = np.ascontiguousarray(np.asarray(image, dtype=np.uint8))
     if a.ndim != 3 or a.shape[2] != 4 or a.size == 0 or max(a.shape[:2]) > MAX_SIDE:
         raise ValueError(f"encode_rgba_lossless_host: expected (H, W, 4) uint8 RGBA, got {a.shape}")
     h, w = a.shape[:2]
-    sym, ctx, vis = model_symbols(a, keep_hidden)
+    sym, ctx, vis = model_symbols(a, keep_hidden, adaptive)
     g = a[..., 1].astype(np.int64)
-    planes = [g, (a[..., 0] - g + 128) & 255, (a[..., 2] - g + 128) & 255]
+    planes = [g, (a[..., 0] - g + 128) & 255, (a[..., 2] - g + 128) & 255,
+              a[..., 0].astype(np.int64), a[..., 2].astype(np.int64)]
+    cost = np.minimum(sym, 256 - sym)
+    ntab = NTAB_ADAPTIVE if adaptive else NTAB
     cls, s, t, lens = [], [], [], []
     blocks = [(r, c) for r in range(0, h, BLOCK) for c in range(0, w, BLOCK)]
     for r, c in blocks:
@@ -229,26 +268,33 @@ def encode_rgba_lossless_host(image, keep_hidden=False):
             continue
         word = 0
         for ch in range(NCH):
-            vals = planes[ch][at][m]                     # raster order
+            kind = ch                                    # the plane this slot holds
+            if adaptive and ch:
+                d, p = planes[ch][at][m], planes[ch + 2][at][m]
+                if (d != d[0]).any() and ((p == p[0]).all()
+                                          or cost[ch + 2][at][m].sum() < cost[ch][at][m].sum()):
+                    kind = ch + 2
+                    word |= (PLAIN_R, PLAIN_B)[ch - 1]
+            vals = planes[kind][at][m]                   # raster order
             if (vals == vals[0]).all():
                 word |= (2 << ch) | (int(vals[0]) << (8 + 8 * ch))
             else:
-                s.append(sym[ch][at][m])
-                t.append(ctx[ch][at][m] + NCTX * ch)
+                s.append(sym[kind][at][m])
+                t.append(ctx[kind][at][m] + NCTX * kind)
                 lens.append(vals.size)
         cls.append(word)
-    freqs = np.zeros((NTAB, 256), dtype=np.int64)
+    freqs = np.zeros((ntab, 256), dtype=np.int64)
     counts, payload = np.zeros(0, np.int32), np.zeros(0, np.uint32)
     if lens:
         s, t, lens = np.concatenate(s), np.concatenate(t), np.asarray(lens, dtype=np.int64)
-        for k in range(NTAB):
+        for k in range(ntab):
             freqs[k] = normalise_counts(np.bincount(s[t == k], minlength=256))
         table = np.stack([np.cumsum(lens) - lens, lens])
         words = encode_table_host(s, t, host_tables(freqs), table, BLOCK * BLOCK)
         counts, payload = words[:lens.size], words[lens.size:].view(np.uint32)
     return build_rgba_lossless(h, w, keep_hidden, alphaexact.encode_alpha_plane_host(a[..., 3]),
                                build_colour(freqs, np.asarray(cls, dtype=np.uint32), counts,
-                                            payload))
+                                            payload), adaptive)
 
 
 # ---- launches
@@ -258,38 +304,43 @@ def _alpha_entries(entries):
 
 
 def _args(wk, keep_hidden, grouped):
-    """The leading arguments of the rgbac_color_exact_* calls from alphaexact's geometry."""
+    """The leading arguments of the rgbac_color_exact_* and rgbac_color_adapt_* calls from
+    alphaexact's geometry."""
     head = (wk.B, wk._descs.data_ptr(), int(keep_hidden))
     mid = (wk.ngroups, wk._groups.data_ptr()) if grouped else ()
     return head + mid + (wk._base.data_ptr(), wk.N)
 
 
-def _encode_colour(dev, sizes, entries, keep_hidden):
+def _encode_colour(dev, sizes, entries, keep_hidden, adaptive=False):
     """The five launches over a ragged batch (classify, histogram, normalise, sizes, encode) and
-    the two host reads -> one colour section per image."""
+    the two host reads -> one colour section per image.  ``adaptive``: the same five of
+    csrc/color_adapt.hip, where choose stands for classify and an image has 25 tables."""
+    fn = "rgbac_color_adapt_" if adaptive else "rgbac_color_exact_"
+    ntab = NTAB_ADAPTIVE if adaptive else NTAB
     wk = alphaexact._Work(sizes, entries, 4, dev)
-    B, N, nf = wk.B, wk.N, NTAB * 256
+    B, N, nf = wk.B, wk.N, ntab * 256
     meta = torch.empty((1 + NCH) * N + B * nf, dtype=torch.int32, device=dev)
     cls, counts, freqs = meta[:N], meta[N:(1 + NCH) * N], meta[(1 + NCH) * N:]
     partials = torch.empty(B * _lib.COLOR_HIST_BLOCKS * nf, dtype=torch.int32, device=dev)
-    tables = torch.empty(B * _lib.COLOR_TABLE_U16, dtype=torch.int16, device=dev)
+    tables = torch.empty(B * (_lib.COLOR_ADAPT_TABLE_U16 if adaptive else _lib.COLOR_TABLE_U16),
+                         dtype=torch.int16, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     plain, grouped = _args(wk, keep_hidden, False), _args(wk, keep_hidden, True)
-    _lib.call("rgbac_color_exact_classify", *grouped, cls.data_ptr(), wk.stream)
-    _lib.call("rgbac_color_exact_tables", *plain, cls.data_ptr(), partials.data_ptr(),
+    _lib.call(fn + ("choose" if adaptive else "classify"), *grouped, cls.data_ptr(), wk.stream)
+    _lib.call(fn + "tables", *plain, cls.data_ptr(), partials.data_ptr(),
               freqs.data_ptr(), tables.data_ptr(), wk.stream)
-    _lib.call("rgbac_color_exact_sizes", *grouped, cls.data_ptr(), tables.data_ptr(),
+    _lib.call(fn + "sizes", *grouped, cls.data_ptr(), tables.data_ptr(),
               counts.data_ptr(), err.data_ptr(), wk.stream)
     ends = torch.cumsum(counts, 0, dtype=torch.int64)
     host = meta.cpu().numpy()                                       # the sizes: one read
     h_cls = host[:N].view(np.uint32)
     h_counts = host[N:(1 + NCH) * N].reshape(N, NCH)
-    h_freqs = host[(1 + NCH) * N:].reshape(B, NTAB, 256)
+    h_freqs = host[(1 + NCH) * N:].reshape(B, ntab, 256)
     cut = np.concatenate([[0], np.cumsum(h_counts.sum(axis=1, dtype=np.int64))])
     total = int(cut[-1])
     words = torch.empty(total + 1, dtype=torch.int32, device=dev)
     if total:
-        _lib.call("rgbac_color_exact_encode", *grouped, cls.data_ptr(), tables.data_ptr(),
+        _lib.call(fn + "encode", *grouped, cls.data_ptr(), tables.data_ptr(),
                   counts.data_ptr(), ends.data_ptr(), words.data_ptr(), total, err.data_ptr(),
                   wk.stream)
     words[total:].copy_(err)
@@ -304,12 +355,15 @@ def _encode_colour(dev, sizes, entries, keep_hidden):
     return out
 
 
-def encode_rgba_lossless(images, keep_hidden=False, device="cuda"):
+def encode_rgba_lossless(images, keep_hidden=False, transform="green", device="cuda"):
     """images: a list of (h, w, 4) uint8 RGBA images of any sizes; GPU tensors are read in place,
     views into larger buffers included -> list[bytes], one RGAL file per image.  A hidden pixel
     (alpha 0) decodes to R = G = B = 0 and its colour bytes do not reach the file;
-    ``keep_hidden`` codes every pixel's colour.  A file does not depend on the images coded with
-    it."""
+    ``keep_hidden`` codes every pixel's colour.  ``transform``: "green" subtracts green from red
+    and blue everywhere (version 1 files); "adaptive" lets each block keep red or blue plain
+    where that codes shorter (version 2 files, smaller where the channels do not move together).
+    A file does not depend on the images coded with it."""
+    adaptive = _adaptive(transform, "encode_rgba_lossless")
     dev = anysize._gpu_device(device)
     _lib.load()
     dev, sizes, entries, keep = anysize._sources(images, dev, "encode_rgba_lossless")
@@ -317,14 +371,14 @@ def encode_rgba_lossless(images, keep_hidden=False, device="cuda"):
         raise ValueError(f"encode_rgba_lossless: an image side is at most {MAX_SIDE}")
     keep_hidden = bool(keep_hidden)
     alpha = alphaexact._encode(dev, sizes, _alpha_entries(entries), 4)
-    colour = _encode_colour(dev, sizes, entries, keep_hidden)
-    return [build_rgba_lossless(h, w, keep_hidden, a, c)
+    colour = _encode_colour(dev, sizes, entries, keep_hidden, adaptive)
+    return [build_rgba_lossless(h, w, keep_hidden, a, c, adaptive)
             for (h, w), a, c in zip(sizes, alpha, colour)]
 
 
-def _decode_colour(parsed, entries, keep_hidden, dev, err):
-    """One launch for parsed files that share ``keep_hidden`` onto the images ``entries``
-    describe (their alpha bytes in place); errors land in ``err``."""
+def _decode_colour(parsed, entries, keep_hidden, dev, err, adaptive=False):
+    """One launch for parsed files that share ``keep_hidden`` and the transform onto the images
+    ``entries`` describe (their alpha bytes in place); errors land in ``err``."""
     sizes = [(f["h"], f["w"]) for f in parsed]
     wk = alphaexact._Work(sizes, entries, 4, dev)
     counts = np.concatenate([f["counts"].reshape(-1) for f in parsed])
@@ -339,16 +393,17 @@ def _decode_colour(parsed, entries, keep_hidden, dev, err):
     tables = _upload(np.concatenate([device_table(f["freqs"]) for f in parsed]).view(np.int16),
                      dev)
     N = wk.N
-    _lib.call("rgbac_color_exact_decode", *_args(wk, keep_hidden, True), ints[:N].data_ptr(),
+    _lib.call("rgbac_color_adapt_decode" if adaptive else "rgbac_color_exact_decode",
+              *_args(wk, keep_hidden, True), ints[:N].data_ptr(),
               tables.data_ptr(), off.data_ptr(), ints[N:(1 + NCH) * N].data_ptr(),
               ints[(1 + NCH) * N:].data_ptr(), int(pbase[-1]), err.data_ptr(), wk.stream)
 
 
 def decode_rgba_lossless(blobs, device="cuda"):
-    """blobs: files from encode_rgba_lossless, any number, any order -> list of (h, w, 4) uint8
-    GPU tensors in the same order.  Every file is parsed and validated on the host before any
-    launch (RuntimeError); one plane-decoder launch puts all alpha planes into the outputs' alpha
-    bytes, one colour launch (two when files with and without keep_hidden are mixed) fills in
+    """blobs: files from encode_rgba_lossless, any number, any order, both transforms -> list of
+    (h, w, 4) uint8 GPU tensors in the same order.  Every file is parsed and validated on the
+    host before any launch (RuntimeError); one plane-decoder launch puts all alpha planes into
+    the outputs' alpha bytes, one colour launch per (version, keep_hidden) present fills in
     R, G, B on the same stream; the one error word is read once at the end."""
     blobs = list(blobs)
     if not blobs:
@@ -361,9 +416,12 @@ def decode_rgba_lossless(blobs, device="cuda"):
     entries = [(t.data_ptr(), f["h"], f["w"], t.stride(0)) for t, f in zip(outs, parsed)]
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     alphaexact._decode([f["alpha"] for f in parsed], _alpha_entries(entries), 4, dev, err)
-    for flag in (False, True):
-        ks = [k for k, f in enumerate(parsed) if f["keep_hidden"] == flag]
-        if ks:
-            _decode_colour([parsed[k] for k in ks], [entries[k] for k in ks], flag, dev, err)
+    for adaptive in (False, True):
+        for flag in (False, True):
+            ks = [k for k, f in enumerate(parsed)
+                  if (f["transform"] == "adaptive", f["keep_hidden"]) == (adaptive, flag)]
+            if ks:
+                _decode_colour([parsed[k] for k in ks], [entries[k] for k in ks], flag, dev, err,
+                               adaptive)
     _raise_code("RGAL file decode", int(err.item()))
     return outs

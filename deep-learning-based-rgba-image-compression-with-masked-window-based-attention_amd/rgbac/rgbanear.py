@@ -128,6 +128,7 @@ def parse_rgba_near(blob):
                                                    colour_len) + blob[HEADER_BYTES:])
     except RuntimeError as e:
         raise RuntimeError(str(e).replace("RGAL file", "RGAN file", 1)) from None
+    del f["transform"]                                      # an RGAN file has no such choice
     q = np.arange(256)
     outside = np.minimum(q, 256 - q) > max_quantised(delta)
     for c in range(NTAB):

@@ -1122,6 +1122,49 @@ int rgbac_color_exact_decode(int batch, const rgbac_image_desc* descs, int keep_
                              const int32_t* counts, const uint32_t* payload,
                              int64_t payload_words, int32_t* err, void* stream);
 
+/* Lossless colour of packed RGBA with the colour transform chosen per block (csrc/color_adapt.hip,
+ * rgbac/rgbalossless.py): the colour half of a version 2 RGAL file.
+ * Arguments, arrays, launches and error codes are those of the rgbac_color_exact_* counterparts
+ * (_choose stands where _classify stood), except:
+ *   cls: bit 4: the red slot (chunk 3 * block + 1, flag bit 2, value bits 16-23) holds plain R
+ *     and not Cr; bit 5: the blue slot holds plain B and not Cb; bits 6, 7 are reserved.
+ *     rgbac_color_adapt_choose takes the difference where it is constant over the block's
+ *     visible pixels, else the plain channel where that is constant, else the plain channel iff
+ *     its cost, the sum over the visible pixels of min(s, 256 - s) of the model's symbols s, is
+ *     strictly the smaller.
+ *   tables: DEVICE uint16[batch * RGBAC_COLOR_ADAPT_TABLE_U16]: 25 tables per image, kind * 5 +
+ *     context, kinds Y, Cr, Cb, R, B; a chunk uses the tables of the kind its slot holds.
+ *   partials: DEVICE uint32[batch * RGBAC_COLOR_HIST_BLOCKS * 6400]; freqs: DEVICE int32[batch *
+ *     6400].
+ *   A class word with a reserved bit, or with bit 4 or 5 beside the hidden bit, is code 3
+ *   (corrupt): the coding kernels skip its block and _decode leaves the block's pixels as they
+ *   are. */
+#define RGBAC_COLOR_ADAPT_KINDS 5
+#define RGBAC_COLOR_ADAPT_TABLE_U16 6426
+int rgbac_color_adapt_choose(int batch, const rgbac_image_desc* descs, int keep_hidden,
+                             int ngroups, const rgbac_alpha_group* groups,
+                             const int32_t* block_base, int total_blocks, uint32_t* cls,
+                             void* stream);
+int rgbac_color_adapt_tables(int batch, const rgbac_image_desc* descs, int keep_hidden,
+                             const int32_t* block_base, int total_blocks, const uint32_t* cls,
+                             uint32_t* partials, int32_t* freqs, uint16_t* tables, void* stream);
+int rgbac_color_adapt_sizes(int batch, const rgbac_image_desc* descs, int keep_hidden,
+                            int ngroups, const rgbac_alpha_group* groups,
+                            const int32_t* block_base, int total_blocks, const uint32_t* cls,
+                            const uint16_t* tables, int32_t* counts, int32_t* err, void* stream);
+int rgbac_color_adapt_encode(int batch, const rgbac_image_desc* descs, int keep_hidden,
+                             int ngroups, const rgbac_alpha_group* groups,
+                             const int32_t* block_base, int total_blocks, const uint32_t* cls,
+                             const uint16_t* tables, const int32_t* counts, const int64_t* ends,
+                             uint32_t* payload, int64_t payload_words, int32_t* err,
+                             void* stream);
+int rgbac_color_adapt_decode(int batch, const rgbac_image_desc* descs, int keep_hidden,
+                             int ngroups, const rgbac_alpha_group* groups,
+                             const int32_t* block_base, int total_blocks, const uint32_t* cls,
+                             const uint16_t* tables, const int64_t* word_off,
+                             const int32_t* counts, const uint32_t* payload,
+                             int64_t payload_words, int32_t* err, void* stream);
+
 /* Near-lossless colour of packed RGBA (csrc/color_near.hip, rgbac/rgbanear.py, DESIGN.md section
  * 28): the colour half of an RGAN file.  Blocks, groups, visibility, contexts, tables, chunk
  * arrays and the class word layout are rgbac_color_exact_*'s; the planes are G, R, B, predicted
