@@ -122,6 +122,8 @@ ALPHA_BLOCK, ALPHA_GROUP, ALPHA_CONTEXTS, ALPHA_HIST_BLOCKS, ALPHA_TABLE_U16 = 1
 COLOR_CHANNELS, COLOR_HIST_BLOCKS, COLOR_TABLE_U16 = 3, 16, 3856
 # RGBAC_COLOR_ADAPT_KINDS, _TABLE_U16
 COLOR_ADAPT_KINDS, COLOR_ADAPT_TABLE_U16 = 5, 6426
+# RGBAC_PALETTE_MAX, _SLICE, _STATE_U32, _RESULT_U32
+PALETTE_MAX, PALETTE_SLICE, PALETTE_STATE_U32, PALETTE_RESULT_U32 = 256, 4096, 516, 258
 # RGBAC_NEAR_MAX_ERROR, _KEEP_HIDDEN, RGBAC_BLEND_COMPOSITE
 NEAR_MAX_ERROR, NEAR_KEEP_HIDDEN, BLEND_COMPOSITE = 16, 256, 512
 
@@ -318,6 +320,11 @@ SIGNATURES = {
                                  _I64, _VP, _VP],
     "rgbac_color_adapt_decode": [_I32, _VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP,
                                  _I64, _VP, _VP],
+    # palette mode of the lossless RGBA files (csrc/color_palette.hip)
+    "rgbac_color_palette_collect": [_I32, _VP, _I32, _I32, _VP, _VP, _VP],
+    "rgbac_color_palette_order": [_I32, _VP, _VP, _VP],
+    "rgbac_color_palette_map": [_I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP],
+    "rgbac_color_palette_unmap": [_I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP],
     # near-lossless colour of packed RGBA (csrc/color_near.hip)
     "rgbac_color_near_settle": [_I32, _VP, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP],
     "rgbac_color_near_tables": [_I32, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP],

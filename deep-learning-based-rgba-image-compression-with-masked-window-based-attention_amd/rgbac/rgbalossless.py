@@ -18,14 +18,23 @@ the model codes in fewer bits: five planes Y, Cr, Cb, R, B with 25 tables (kind 
 class word bit 4 / 5 = the red / blue slot holds the plain channel.  Such files are version 2;
 ``transform="green"``, the default, writes what it always wrote.
 
+``transform="palette"`` (csrc/color_palette.hip) writes an image that has
+at most 256 distinct pixels as a version 3 file: its palette and one plane of palette positions,
+an ``RGAP`` blob like the alpha plane.  Every other image of the call is written as
+``transform="adaptive"`` writes it.  A pixel is its little-endian dword (R low, A high), 0 where
+alpha is 0 unless ``keep_hidden``; the palette is ascending by (A, (R + 2 G + B) >> 2, dword).
+
 File, little-endian:
-    "RGAL", u16 version (1; 2 adaptive), u16 flags (bit 0: keep_hidden; bit 1: adaptive, set in
-    every version 2 file and in no other), u32 h, u32 w, u32 alpha bytes, u32 colour bytes; the
+    "RGAL", u16 version (1; 2 adaptive; 3 palette), u16 flags (bit 0: keep_hidden; bit 1:
+    adaptive, set in every version 2 file and in no other; bit 2: palette, likewise for version
+    3), u32 h, u32 w, u32 alpha bytes, u32 colour bytes; the
     RGAP blob; the colour section: u32 chunks, u32 payload words; 15 tables (25 in version 2) in
     the RGAP table form, channel-major (kind-major); one u32 class word per block, row-major (bit
     0 hidden, bits 1-3 channel Y / Cr / Cb constant, version 2: bits 4 / 5 plain R / B, bits
     8-15 / 16-23 / 24-31 the constants); one u16 word count per chunk (block-major, Y, Cr, Cb);
     the payload, u32 words.
+    Version 3: alpha bytes is 0 and there is no alpha blob (the alpha lies in the palette); the
+    colour section is u32 n in 1..256, n palette dwords, the RGAP blob of the (h, w) index plane.
 """
 import struct
 
@@ -40,8 +49,12 @@ MAGIC = b"RGAL"
 VERSION = 1
 VERSION_ADAPTIVE = 2
 FLAG_KEEP_HIDDEN = 1
+VERSION_PALETTE = 3
 FLAG_ADAPTIVE = 2
-TRANSFORMS = ("green", "adaptive")    # by version - 1
+FLAG_PALETTE = 4
+TRANSFORMS = ("green", "adaptive")    # the colour transforms any image can be written with
+TRANSFORM_NAMES = TRANSFORMS + ("palette",)   # every value of ``transform``, by version - 1
+PALETTE_MAX = _lib.PALETTE_MAX        # colours of a version 3 file
 NCH = _lib.COLOR_CHANNELS
 NCTX = alphaexact.NCTX
 NTAB = NCH * NCTX                     # 15 tables: channel * 5 + context
@@ -102,15 +115,57 @@ def build_rgba_lossless(h, w, keep_hidden, alpha, colour, adaptive=False):
                         len(alpha), len(colour)) + alpha + colour
 
 
-def _adaptive(transform, who):
-    if transform not in TRANSFORMS:
-        raise ValueError(f"{who}: transform must be one of {TRANSFORMS}, got {transform!r}")
-    return transform == "adaptive"
+def build_rgba_palette(h, w, keep_hidden, palette, plane):
+    """One version 3 file from its palette (canonical dwords in the format's order) and the RGAP
+    blob of its index plane."""
+    colour = struct.pack("<I", len(palette)) + np.asarray(palette).astype("<u4").tobytes() + plane
+    return _HEADER.pack(MAGIC, VERSION_PALETTE, FLAG_PALETTE | (FLAG_KEEP_HIDDEN if keep_hidden
+                                                                 else 0), h, w, 0,
+                        len(colour)) + colour
+
+
+def palette_key(dwords):
+    """Canonical pixel dwords -> the uint64 keys a palette is ascending by:
+    A << 40 | ((R + 2 G + B) >> 2) << 32 | dword."""
+    v = np.asarray(dwords).astype(np.uint64)
+    luma = ((v & 255) + 2 * ((v >> 8) & 255) + ((v >> 16) & 255)) >> 2
+    return ((v >> 24) << 40) | (luma << 32) | v
+
+
+def _transform(transform, who):
+    if transform not in TRANSFORM_NAMES:
+        raise ValueError(f"{who}: transform must be one of {TRANSFORM_NAMES}, got {transform!r}")
+    return transform
+
+
+def _parse_palette(blob, flags, h, w, alpha_len, bad):
+    """The rest of parse_rgba_lossless for a version 3 file (header and total length checked)."""
+    if alpha_len:
+        raise bad(f"a version 3 file has no alpha section, the header says {alpha_len} bytes")
+    sec = blob[HEADER_BYTES:]
+    if len(sec) < 4:
+        raise bad("the colour section is truncated in the palette")
+    n = struct.unpack_from("<I", sec)[0]
+    if not 1 <= n <= PALETTE_MAX:
+        raise bad(f"a palette of {n} colours")
+    if len(sec) < 4 + 4 * n:
+        raise bad("the colour section is truncated in the palette")
+    palette = np.frombuffer(sec, dtype="<u4", count=n, offset=4).astype(np.uint32)
+    if (np.diff(palette_key(palette).astype(np.int64)) <= 0).any():
+        raise bad("the palette is not strictly ascending")
+    if not flags & FLAG_KEEP_HIDDEN and ((palette >> 24 == 0) & (palette != 0)).any():
+        raise bad("a hidden palette entry with a colour, without keep_hidden")
+    plane = alphaexact.parse_alpha_planes(sec[4 + 4 * n:])
+    if (plane["h"], plane["w"]) != (h, w):
+        raise bad(f"the index plane is {plane['h']}x{plane['w']}, the image {h}x{w}")
+    return {"h": h, "w": w, "keep_hidden": bool(flags & FLAG_KEEP_HIDDEN), "transform": "palette",
+            "palette": palette, "plane": plane}
 
 
 def parse_rgba_lossless(blob):
     """bytes -> {"h", "w", "keep_hidden", "transform" ("green": version 1, "adaptive": version
-    2), "alpha": the parsed RGAP blob, "freqs" (15, 256) int64, (25, 256) if adaptive, "cls"
+    2, "palette": version 3), and for a version 3 file "palette": uint32 canonical pixels, "plane":
+    the parsed RGAP blob of the index plane; for the others "alpha": the parsed RGAP blob, "freqs" (15, 256) int64, (25, 256) if adaptive, "cls"
     uint32 per block, "counts" int32 (blocks, 3) (0 where there is no chunk), "payload"
     uint32}.  Pure host code; raises RuntimeError on anything wrong: bad magic, version, flags or
     size (flags bit 1 belongs to version 2, which always has it; class bits 4 and 5 to version 2,
@@ -119,7 +174,10 @@ def parse_rgba_lossless(blob):
     parse_alpha_planes rejects or of another size; tables that are not fixed points of
     normalise_counts; class words with reserved bits set, a hidden word that is not 1 or a value
     byte under a clear flag; a chunk table whose length is not what the class words imply; word
-    counts outside [2, block pixels / 2 + 3] or that do not sum to the payload."""
+    counts outside [2, block pixels / 2 + 3] or that do not sum to the payload.  Version 3: flags
+    other than bit 2 (always) and bit 0; an alpha section; a palette of 0 or more than 256
+    colours, not strictly ascending in its key, or, without keep_hidden, with an entry of alpha
+    0 that is not 0; an index plane parse_alpha_planes rejects or of another size."""
     blob = bytes(blob)
 
     def bad(msg):
@@ -130,13 +188,17 @@ def parse_rgba_lossless(blob):
     magic, version, flags, h, w, alpha_len, colour_len = _HEADER.unpack_from(blob)
     if magic != MAGIC:
         raise bad("bad magic (not an RGAL file)")
-    if version not in (VERSION, VERSION_ADAPTIVE):
+    if version not in (VERSION, VERSION_ADAPTIVE, VERSION_PALETTE):
         raise bad(f"unsupported version {version}")
     adaptive = version == VERSION_ADAPTIVE
     if adaptive and not flags & FLAG_ADAPTIVE:
         raise bad(f"unsupported version {version} with flags {flags:#x} (a version 2 file has "
                   "bit 1, the adaptive transform)")
-    if flags & ~(FLAG_KEEP_HIDDEN | (FLAG_ADAPTIVE if adaptive else 0)):
+    if version == VERSION_PALETTE and not flags & FLAG_PALETTE:
+        raise bad(f"unsupported version {version} with flags {flags:#x} (a version 3 file has "
+                  "bit 2, the palette)")
+    own = {VERSION: 0, VERSION_ADAPTIVE: FLAG_ADAPTIVE, VERSION_PALETTE: FLAG_PALETTE}[version]
+    if flags & ~(FLAG_KEEP_HIDDEN | own):
         raise bad(f"unknown flags {flags:#x} in a version {version} file")
     ntab = NTAB_ADAPTIVE if adaptive else NTAB
     if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
@@ -145,6 +207,8 @@ def parse_rgba_lossless(blob):
     if total != len(blob):
         raise bad(f"{'truncated' if len(blob) < total else 'over-long'}: the section lengths say "
                   f"{total} bytes, the file has {len(blob)}")
+    if version == VERSION_PALETTE:
+        return _parse_palette(blob, flags, h, w, alpha_len, bad)
     alpha = alphaexact.parse_alpha_planes(blob[HEADER_BYTES:HEADER_BYTES + alpha_len])
     if (alpha["h"], alpha["w"]) != (h, w):
         raise bad(f"the alpha plane is {alpha['h']}x{alpha['w']}, the image {h}x{w}")
@@ -247,11 +311,23 @@ def encode_rgba_lossless_host(image, keep_hidden=False, transform="green"):
     """encode_rgba_lossless for one image on the CPU: the kernels' byte-level reference (not a
     fallback; the device path never calls it)."""
     from .ans import encode_table_host
-    adaptive = _adaptive(transform, "encode_rgba_lossless_host")
+    transform = _transform(transform, "encode_rgba_lossless_host")
     a = np.ascontiguousarray(np.asarray(image, dtype=np.uint8))
     if a.ndim != 3 or a.shape[2] != 4 or a.size == 0 or max(a.shape[:2]) > MAX_SIDE:
         raise ValueError(f"encode_rgba_lossless_host: expected (H, W, 4) uint8 RGBA, got {a.shape}")
     h, w = a.shape[:2]
+    if transform == "palette":
+        px = a.view("<u4")[..., 0].astype(np.uint32)
+        if not keep_hidden:
+            px = np.where(a[..., 3] == 0, np.uint32(0), px)
+        colours, index = np.unique(px, return_inverse=True)          # ascending by dword
+        if colours.size <= PALETTE_MAX:
+            order = np.argsort(palette_key(colours))
+            rank = np.empty(colours.size, dtype=np.uint8)
+            rank[order] = np.arange(colours.size)
+            plane = alphaexact.encode_alpha_plane_host(rank[index.reshape(h, w)])
+            return build_rgba_palette(h, w, keep_hidden, colours[order], plane)
+    adaptive = transform != "green"
     sym, ctx, vis = model_symbols(a, keep_hidden, adaptive)
     g = a[..., 1].astype(np.int64)
     planes = [g, (a[..., 0] - g + 128) & 255, (a[..., 2] - g + 128) & 255,
@@ -355,25 +431,79 @@ def _encode_colour(dev, sizes, entries, keep_hidden, adaptive=False):
     return out
 
 
+def _slices(sizes):
+    return max(-(-h * w // _lib.PALETTE_SLICE) for h, w in sizes)
+
+
+def _planes(sizes, dev):
+    """One dense uint8 index plane per image, 16-byte aligned -> (the buffer, the planes as
+    views, their descriptor entries)."""
+    cut = np.concatenate([[0], np.cumsum([-(-h * w // 16) * 16 for h, w in sizes])])
+    flat = torch.empty(int(cut[-1]), dtype=torch.uint8, device=dev)
+    views = [flat[int(cut[i]):int(cut[i]) + h * w].view(h, w) for i, (h, w) in enumerate(sizes)]
+    return flat, views, [(v.data_ptr(), h, w, w) for v, (h, w) in zip(views, sizes)]
+
+
+def _encode_palette(dev, sizes, entries, keep_hidden):
+    """The three launches over a ragged batch (collect, order, map), one read-back of every
+    image's overflow word, colour count and palette, then the plane coder over the index planes
+    of the images that have a palette -> per image (palette uint32, RGAP blob), or None where
+    the image has more than 256 colours."""
+    B, stream = len(sizes), _lib.stream_ptr(dev)
+    descs = anysize._upload_descs(entries, dev)
+    flat, views, pentries = _planes(sizes, dev)
+    pdescs = anysize._upload_descs(pentries, dev)
+    state = torch.zeros(B * _lib.PALETTE_STATE_U32, dtype=torch.int32, device=dev)
+    result = torch.zeros(B * _lib.PALETTE_RESULT_U32 + 1, dtype=torch.int32, device=dev)
+    err = result[-1:]
+    _lib.call("rgbac_color_palette_collect", B, descs.data_ptr(), int(keep_hidden),
+              _slices(sizes), state.data_ptr(), err.data_ptr(), stream)
+    _lib.call("rgbac_color_palette_order", B, state.data_ptr(), result.data_ptr(), stream)
+    _lib.call("rgbac_color_palette_map", B, descs.data_ptr(), pdescs.data_ptr(),
+              int(keep_hidden), _slices(sizes), result.data_ptr(), err.data_ptr(), stream)
+    host = result.cpu().numpy()                                     # the one read-back
+    _raise_code("encode_rgba_lossless (palette)", int(host[-1]))
+    host = host[:-1].view(np.uint32).reshape(B, _lib.PALETTE_RESULT_U32)
+    ks = [k for k in range(B) if not host[k, 0]]
+    out = [None] * B
+    if ks:
+        blobs = alphaexact._encode(dev, [sizes[k] for k in ks], [pentries[k] for k in ks], 1)
+        for k, blob in zip(ks, blobs):
+            out[k] = (host[k, 2:2 + int(host[k, 1])].copy(), blob)
+    return out
+
+
 def encode_rgba_lossless(images, keep_hidden=False, transform="green", device="cuda"):
     """images: a list of (h, w, 4) uint8 RGBA images of any sizes; GPU tensors are read in place,
     views into larger buffers included -> list[bytes], one RGAL file per image.  A hidden pixel
     (alpha 0) decodes to R = G = B = 0 and its colour bytes do not reach the file;
     ``keep_hidden`` codes every pixel's colour.  ``transform``: "green" subtracts green from red
     and blue everywhere (version 1 files); "adaptive" lets each block keep red or blue plain
-    where that codes shorter (version 2 files, smaller where the channels do not move together).
+    where that codes shorter (version 2 files, smaller where the channels do not move together);
+    "palette" writes an image of at most 256 distinct pixels as its palette and one plane of
+    palette positions (version 3 files) and every other image as "adaptive" does.
     A file does not depend on the images coded with it."""
-    adaptive = _adaptive(transform, "encode_rgba_lossless")
+    transform = _transform(transform, "encode_rgba_lossless")
+    adaptive = transform != "green"
     dev = anysize._gpu_device(device)
     _lib.load()
     dev, sizes, entries, keep = anysize._sources(images, dev, "encode_rgba_lossless")
     if max(max(s) for s in sizes) > MAX_SIDE:
         raise ValueError(f"encode_rgba_lossless: an image side is at most {MAX_SIDE}")
     keep_hidden = bool(keep_hidden)
-    alpha = alphaexact._encode(dev, sizes, _alpha_entries(entries), 4)
-    colour = _encode_colour(dev, sizes, entries, keep_hidden, adaptive)
-    return [build_rgba_lossless(h, w, keep_hidden, a, c, adaptive)
-            for (h, w), a, c in zip(sizes, alpha, colour)]
+    files = [None] * len(sizes)
+    if transform == "palette":
+        for k, found in enumerate(_encode_palette(dev, sizes, entries, keep_hidden)):
+            if found:
+                files[k] = build_rgba_palette(*sizes[k], keep_hidden, *found)
+    ks = [k for k, f in enumerate(files) if f is None]
+    if ks:
+        sizes, entries = [sizes[k] for k in ks], [entries[k] for k in ks]
+        alpha = alphaexact._encode(dev, sizes, _alpha_entries(entries), 4)
+        colour = _encode_colour(dev, sizes, entries, keep_hidden, adaptive)
+        for k, (h, w), a, c in zip(ks, sizes, alpha, colour):
+            files[k] = build_rgba_lossless(h, w, keep_hidden, a, c, adaptive)
+    return files
 
 
 def _decode_colour(parsed, entries, keep_hidden, dev, err, adaptive=False):
@@ -399,12 +529,31 @@ def _decode_colour(parsed, entries, keep_hidden, dev, err, adaptive=False):
               ints[(1 + NCH) * N:].data_ptr(), int(pbase[-1]), err.data_ptr(), wk.stream)
 
 
+def _decode_palette(parsed, entries, dev, err):
+    """Version 3 files onto the images ``entries`` describe: one plane-decoder launch into index
+    planes of their own, one unmap launch behind it on the same stream."""
+    sizes = [(f["h"], f["w"]) for f in parsed]
+    flat, views, pentries = _planes(sizes, dev)
+    alphaexact._decode([f["plane"] for f in parsed], pentries, 1, dev, err)
+    palettes = np.zeros((len(parsed), PALETTE_MAX), dtype=np.uint32)
+    for k, f in enumerate(parsed):
+        palettes[k, :f["palette"].size] = f["palette"]
+    palettes = _upload(palettes.view(np.int32), dev)
+    counts = _upload(np.array([f["palette"].size for f in parsed], dtype=np.int32), dev)
+    descs, pdescs = anysize._upload_descs(entries, dev), anysize._upload_descs(pentries, dev)
+    _lib.call("rgbac_color_palette_unmap", len(parsed), descs.data_ptr(), pdescs.data_ptr(),
+              _slices(sizes), palettes.data_ptr(), counts.data_ptr(), err.data_ptr(),
+              _lib.stream_ptr(dev))
+
+
 def decode_rgba_lossless(blobs, device="cuda"):
-    """blobs: files from encode_rgba_lossless, any number, any order, both transforms -> list of
+    """blobs: files from encode_rgba_lossless, any number, any order, every transform -> list of
     (h, w, 4) uint8 GPU tensors in the same order.  Every file is parsed and validated on the
     host before any launch (RuntimeError); one plane-decoder launch puts all alpha planes into
     the outputs' alpha bytes, one colour launch per (version, keep_hidden) present fills in
-    R, G, B on the same stream; the one error word is read once at the end."""
+    R, G, B on the same stream; version 3 files have a plane-decoder launch for their index
+    planes and one launch that writes whole pixels from them; the one error word is read once at
+    the end."""
     blobs = list(blobs)
     if not blobs:
         raise ValueError("decode_rgba_lossless: no files")
@@ -415,11 +564,17 @@ def decode_rgba_lossless(blobs, device="cuda"):
     dev = outs[0].device
     entries = [(t.data_ptr(), f["h"], f["w"], t.stride(0)) for t, f in zip(outs, parsed)]
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    alphaexact._decode([f["alpha"] for f in parsed], _alpha_entries(entries), 4, dev, err)
+    ks = [k for k, f in enumerate(parsed) if f["transform"] == "palette"]
+    if ks:
+        _decode_palette([parsed[k] for k in ks], [entries[k] for k in ks], dev, err)
+    ks = [k for k, f in enumerate(parsed) if f["transform"] != "palette"]
+    if ks:
+        alphaexact._decode([parsed[k]["alpha"] for k in ks],
+                           _alpha_entries([entries[k] for k in ks]), 4, dev, err)
     for adaptive in (False, True):
         for flag in (False, True):
             ks = [k for k, f in enumerate(parsed)
-                  if (f["transform"] == "adaptive", f["keep_hidden"]) == (adaptive, flag)]
+                  if (f["transform"], f["keep_hidden"]) == (TRANSFORMS[adaptive], flag)]
             if ks:
                 _decode_colour([parsed[k] for k in ks], [entries[k] for k in ks], flag, dev, err,
                                adaptive)

@@ -1165,6 +1165,48 @@ int rgbac_color_adapt_decode(int batch, const rgbac_image_desc* descs, int keep_
                              const int32_t* counts, const uint32_t* payload,
                              int64_t payload_words, int32_t* err, void* stream);
 
+/* Palette mode of the lossless RGBA files (csrc/color_palette.hip, rgbac/rgbalossless.py,
+ * DESIGN.md section 31): the device side of a version 3 RGAL file.  A pixel is its little-endian
+ * dword R | G << 8 | B << 16 | A << 24, canonical: 0 where alpha is 0 unless keep_hidden.  An
+ * image with at most RGBAC_PALETTE_MAX distinct canonical pixels gets a palette, ascending by the
+ * key A << 40 | ((R + 2 G + B) >> 2) << 32 | dword, and a dense uint8 plane of palette positions
+ * for the plane coder above.
+ *   descs: DEVICE array of `batch` rgbac_image_desc, ptr = the first RGBA pixel, 4-byte aligned,
+ *     sides in [1, 32767], row_stride_bytes a multiple of 4 and at least 4 w; every pixel is read
+ *     and written as a whole dword, four at a time (16 bytes) where the rows lie back to back and
+ *     ptr is 16-byte aligned.
+ *   planes: DEVICE array of `batch` rgbac_image_desc, the index plane of each image: ptr 4-byte
+ *     aligned, the image's h and w, row_stride_bytes = w.
+ *   slices: the grid's first dimension, at least ceil(h w / RGBAC_PALETTE_SLICE) of the largest
+ *     image.
+ *   state: DEVICE uint32[batch * RGBAC_PALETTE_STATE_U32], ZEROED by the caller: per image an
+ *     open-addressing set of RGBAC_PALETTE_SLOTS dwords (0: empty), the count of its colours, the
+ *     overflow word, the flag for the pixel 0, one unused word.
+ *   result: DEVICE uint32[batch * RGBAC_PALETTE_RESULT_U32]: per image overflow (1: more than
+ *     256 colours, or an image collect could not read), n, palette[256] (0 from n on).
+ *   err: DEVICE int32, zeroed by the caller, first non-zero code wins.  5: a descriptor that does
+ *     not hold together (nothing of its image is touched); 3: _map met a pixel that is not in the
+ *     palette (position 0 is stored), _unmap a position >= n (the dword 0 is written).
+ * rgbac_color_palette_collect, _order, _map: three launches on one stream, no host step between
+ *   them; _map skips the images whose overflow is set.
+ * rgbac_color_palette_unmap: palettes: DEVICE uint32[batch * 256], counts: DEVICE int32[batch] in
+ *   [1, 256]; rewrites every pixel of every image from its index plane. */
+#define RGBAC_PALETTE_MAX 256
+#define RGBAC_PALETTE_SLOTS 512
+#define RGBAC_PALETTE_SLICE 4096
+#define RGBAC_PALETTE_STATE_U32 516
+#define RGBAC_PALETTE_RESULT_U32 258
+int rgbac_color_palette_collect(int batch, const rgbac_image_desc* descs, int keep_hidden,
+                                int slices, uint32_t* state, int32_t* err, void* stream);
+int rgbac_color_palette_order(int batch, const uint32_t* state, uint32_t* result, void* stream);
+int rgbac_color_palette_map(int batch, const rgbac_image_desc* descs,
+                            const rgbac_image_desc* planes, int keep_hidden, int slices,
+                            const uint32_t* result, int32_t* err, void* stream);
+int rgbac_color_palette_unmap(int batch, const rgbac_image_desc* descs,
+                              const rgbac_image_desc* planes, int slices,
+                              const uint32_t* palettes, const int32_t* counts, int32_t* err,
+                              void* stream);
+
 /* Near-lossless colour of packed RGBA (csrc/color_near.hip, rgbac/rgbanear.py, DESIGN.md section
  * 28): the colour half of an RGAN file.  Blocks, groups, visibility, contexts, tables, chunk
  * arrays and the class word layout are rgbac_color_exact_*'s; the planes are G, R, B, predicted
