@@ -124,6 +124,8 @@ COLOR_CHANNELS, COLOR_HIST_BLOCKS, COLOR_TABLE_U16 = 3, 16, 3856
 COLOR_ADAPT_KINDS, COLOR_ADAPT_TABLE_U16 = 5, 6426
 # RGBAC_PALETTE_MAX, _SLICE, _STATE_U32, _RESULT_U32
 PALETTE_MAX, PALETTE_SLICE, PALETTE_STATE_U32, PALETTE_RESULT_U32 = 256, 4096, 516, 258
+# RGBAC_INDEX_CONTEXTS, _SYMBOLS, _HIST_BLOCKS, _TABLE_U16
+INDEX_CONTEXTS, INDEX_SYMBOLS, INDEX_HIST_BLOCKS, INDEX_TABLE_U16 = 64, 5, 16, 576
 # RGBAC_NEAR_MAX_ERROR, _KEEP_HIDDEN, RGBAC_BLEND_COMPOSITE
 NEAR_MAX_ERROR, NEAR_KEEP_HIDDEN, BLEND_COMPOSITE = 16, 256, 512
 
@@ -325,6 +327,13 @@ SIGNATURES = {
     "rgbac_color_palette_order": [_I32, _VP, _VP, _VP],
     "rgbac_color_palette_map": [_I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP],
     "rgbac_color_palette_unmap": [_I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP],
+    # palette index planes (csrc/index_exact.hip)
+    "rgbac_index_exact_tables": [_I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP],
+    "rgbac_index_exact_sizes": [_I32, _VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP],
+    "rgbac_index_exact_encode": [_I32, _VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _I64,
+                                 _VP, _VP],
+    "rgbac_index_exact_decode": [_I32, _VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _I64,
+                                 _VP, _VP],
     # near-lossless colour of packed RGBA (csrc/color_near.hip)
     "rgbac_color_near_settle": [_I32, _VP, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP],
     "rgbac_color_near_tables": [_I32, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP],

@@ -24,8 +24,13 @@ an ``RGAP`` blob like the alpha plane.  Every other image of the call is written
 ``transform="adaptive"`` writes it.  A pixel is its little-endian dword (R low, A high), 0 where
 alpha is 0 unless ``keep_hidden``; the palette is ascending by (A, (R + 2 G + B) >> 2, dword).
 
+``index_model="neighbour"`` (csrc/index_exact.hip) codes that plane of
+positions as labels instead: which neighbour a pixel equals, an ``RGAI`` blob of
+rgbac.indexexact.  Such files are version 4; ``index_model="plane"``, the default, writes what
+palette mode always wrote.
+
 File, little-endian:
-    "RGAL", u16 version (1; 2 adaptive; 3 palette), u16 flags (bit 0: keep_hidden; bit 1:
+    "RGAL", u16 version (1; 2 adaptive; 3 palette; 4 palette, neighbour model), u16 flags (bit 0: keep_hidden; bit 1:
     adaptive, set in every version 2 file and in no other; bit 2: palette, likewise for version
     3), u32 h, u32 w, u32 alpha bytes, u32 colour bytes; the
     RGAP blob; the colour section: u32 chunks, u32 payload words; 15 tables (25 in version 2) in
@@ -35,13 +40,15 @@ File, little-endian:
     the payload, u32 words.
     Version 3: alpha bytes is 0 and there is no alpha blob (the alpha lies in the palette); the
     colour section is u32 n in 1..256, n palette dwords, the RGAP blob of the (h, w) index plane.
+    Version 4: as version 3 with flags bit 2 and bit 3 (the neighbour model) always set, and the
+    RGAI blob of the index plane, whose n is the palette's, in the RGAP blob's place.
 """
 import struct
 
 import numpy as np
 import torch
 
-from . import _lib, alphaexact, anysize
+from . import _lib, alphaexact, anysize, indexexact
 from .alphaexact import BLOCK, MAX_SIDE, SPARSE_MAX, TOTAL, block_grid, normalise_counts
 from .ans import _raise_code, _upload
 
@@ -52,6 +59,9 @@ FLAG_KEEP_HIDDEN = 1
 VERSION_PALETTE = 3
 FLAG_ADAPTIVE = 2
 FLAG_PALETTE = 4
+VERSION_NEIGHBOUR = 4                 # palette mode, the index plane as an RGAI blob
+FLAG_NEIGHBOUR = 8
+INDEX_MODELS = ("plane", "neighbour")
 TRANSFORMS = ("green", "adaptive")    # the colour transforms any image can be written with
 TRANSFORM_NAMES = TRANSFORMS + ("palette",)   # every value of ``transform``, by version - 1
 PALETTE_MAX = _lib.PALETTE_MAX        # colours of a version 3 file
@@ -115,13 +125,15 @@ def build_rgba_lossless(h, w, keep_hidden, alpha, colour, adaptive=False):
                         len(alpha), len(colour)) + alpha + colour
 
 
-def build_rgba_palette(h, w, keep_hidden, palette, plane):
+def build_rgba_palette(h, w, keep_hidden, palette, plane, neighbour=False):
     """One version 3 file from its palette (canonical dwords in the format's order) and the RGAP
-    blob of its index plane."""
+    blob of its index plane; ``neighbour``: a version 4 file, ``plane`` the RGAI blob."""
     colour = struct.pack("<I", len(palette)) + np.asarray(palette).astype("<u4").tobytes() + plane
-    return _HEADER.pack(MAGIC, VERSION_PALETTE, FLAG_PALETTE | (FLAG_KEEP_HIDDEN if keep_hidden
-                                                                 else 0), h, w, 0,
-                        len(colour)) + colour
+    flags = FLAG_PALETTE | (FLAG_KEEP_HIDDEN if keep_hidden else 0)
+    if neighbour:
+        return _HEADER.pack(MAGIC, VERSION_NEIGHBOUR, flags | FLAG_NEIGHBOUR, h, w, 0,
+                            len(colour)) + colour
+    return _HEADER.pack(MAGIC, VERSION_PALETTE, flags, h, w, 0, len(colour)) + colour
 
 
 def palette_key(dwords):
@@ -138,10 +150,19 @@ def _transform(transform, who):
     return transform
 
 
+def _index_model(index_model, who):
+    if index_model not in INDEX_MODELS:
+        raise ValueError(f"{who}: index_model must be one of {INDEX_MODELS}, got {index_model!r}")
+    return index_model == "neighbour"
+
+
 def _parse_palette(blob, flags, h, w, alpha_len, bad):
-    """The rest of parse_rgba_lossless for a version 3 file (header and total length checked)."""
+    """The rest of parse_rgba_lossless for a version 3 or 4 file (header and total length
+    checked)."""
+    neighbour = bool(flags & FLAG_NEIGHBOUR)
     if alpha_len:
-        raise bad(f"a version 3 file has no alpha section, the header says {alpha_len} bytes")
+        raise bad(f"a version {3 + neighbour} file has no alpha section, the header says "
+                  f"{alpha_len} bytes")
     sec = blob[HEADER_BYTES:]
     if len(sec) < 4:
         raise bad("the colour section is truncated in the palette")
@@ -155,11 +176,19 @@ def _parse_palette(blob, flags, h, w, alpha_len, bad):
         raise bad("the palette is not strictly ascending")
     if not flags & FLAG_KEEP_HIDDEN and ((palette >> 24 == 0) & (palette != 0)).any():
         raise bad("a hidden palette entry with a colour, without keep_hidden")
-    plane = alphaexact.parse_alpha_planes(sec[4 + 4 * n:])
+    if neighbour:
+        plane = indexexact.parse_index_planes(sec[4 + 4 * n:])
+        if plane["n"] != n:
+            raise bad(f"the index plane is of {plane['n']} positions, the palette has {n}")
+    else:
+        plane = alphaexact.parse_alpha_planes(sec[4 + 4 * n:])
     if (plane["h"], plane["w"]) != (h, w):
         raise bad(f"the index plane is {plane['h']}x{plane['w']}, the image {h}x{w}")
-    return {"h": h, "w": w, "keep_hidden": bool(flags & FLAG_KEEP_HIDDEN), "transform": "palette",
-            "palette": palette, "plane": plane}
+    out = {"h": h, "w": w, "keep_hidden": bool(flags & FLAG_KEEP_HIDDEN), "transform": "palette",
+           "palette": palette, "plane": plane}
+    if neighbour:
+        out["index_model"] = "neighbour"
+    return out
 
 
 def parse_rgba_lossless(blob):
@@ -177,7 +206,10 @@ def parse_rgba_lossless(blob):
     counts outside [2, block pixels / 2 + 3] or that do not sum to the payload.  Version 3: flags
     other than bit 2 (always) and bit 0; an alpha section; a palette of 0 or more than 256
     colours, not strictly ascending in its key, or, without keep_hidden, with an entry of alpha
-    0 that is not 0; an index plane parse_alpha_planes rejects or of another size."""
+    0 that is not 0; an index plane parse_alpha_planes rejects or of another size.  Version 4: as
+    version 3 with "index_model": "neighbour" and "plane" the parsed RGAI blob; flags without bits
+    2 and 3 (bit 3 belongs to version 4 alone); an index plane parse_index_planes rejects, of
+    another size or of another n than the palette's."""
     blob = bytes(blob)
 
     def bad(msg):
@@ -188,8 +220,11 @@ def parse_rgba_lossless(blob):
     magic, version, flags, h, w, alpha_len, colour_len = _HEADER.unpack_from(blob)
     if magic != MAGIC:
         raise bad("bad magic (not an RGAL file)")
-    if version not in (VERSION, VERSION_ADAPTIVE, VERSION_PALETTE):
+    if version not in (VERSION, VERSION_ADAPTIVE, VERSION_PALETTE, VERSION_NEIGHBOUR):
         raise bad(f"unsupported version {version}")
+    if version == VERSION_NEIGHBOUR and flags & 12 != FLAG_PALETTE | FLAG_NEIGHBOUR:
+        raise bad(f"unsupported version {version} with flags {flags:#x} (a version 4 file has "
+                  "bits 2 and 3, the palette and the neighbour model)")
     adaptive = version == VERSION_ADAPTIVE
     if adaptive and not flags & FLAG_ADAPTIVE:
         raise bad(f"unsupported version {version} with flags {flags:#x} (a version 2 file has "
@@ -197,7 +232,8 @@ def parse_rgba_lossless(blob):
     if version == VERSION_PALETTE and not flags & FLAG_PALETTE:
         raise bad(f"unsupported version {version} with flags {flags:#x} (a version 3 file has "
                   "bit 2, the palette)")
-    own = {VERSION: 0, VERSION_ADAPTIVE: FLAG_ADAPTIVE, VERSION_PALETTE: FLAG_PALETTE}[version]
+    own = {VERSION: 0, VERSION_ADAPTIVE: FLAG_ADAPTIVE, VERSION_PALETTE: FLAG_PALETTE,
+           VERSION_NEIGHBOUR: FLAG_PALETTE | FLAG_NEIGHBOUR}[version]
     if flags & ~(FLAG_KEEP_HIDDEN | own):
         raise bad(f"unknown flags {flags:#x} in a version {version} file")
     ntab = NTAB_ADAPTIVE if adaptive else NTAB
@@ -207,7 +243,7 @@ def parse_rgba_lossless(blob):
     if total != len(blob):
         raise bad(f"{'truncated' if len(blob) < total else 'over-long'}: the section lengths say "
                   f"{total} bytes, the file has {len(blob)}")
-    if version == VERSION_PALETTE:
+    if version in (VERSION_PALETTE, VERSION_NEIGHBOUR):
         return _parse_palette(blob, flags, h, w, alpha_len, bad)
     alpha = alphaexact.parse_alpha_planes(blob[HEADER_BYTES:HEADER_BYTES + alpha_len])
     if (alpha["h"], alpha["w"]) != (h, w):
@@ -307,11 +343,12 @@ def model_symbols(image, keep_hidden=False, adaptive=False):
     return ((v - pred) & 255).astype(np.int32), ctx.astype(np.int32), vis
 
 
-def encode_rgba_lossless_host(image, keep_hidden=False, transform="green"):
+def encode_rgba_lossless_host(image, keep_hidden=False, transform="green", index_model="plane"):
     """encode_rgba_lossless for one image on the CPU: the kernels' byte-level reference (not a
     fallback; the device path never calls it)."""
     from .ans import encode_table_host
     transform = _transform(transform, "encode_rgba_lossless_host")
+    neighbour = transform == "palette" and _index_model(index_model, "encode_rgba_lossless_host")
     a = np.ascontiguousarray(np.asarray(image, dtype=np.uint8))
     if a.ndim != 3 or a.shape[2] != 4 or a.size == 0 or max(a.shape[:2]) > MAX_SIDE:
         raise ValueError(f"encode_rgba_lossless_host: expected (H, W, 4) uint8 RGBA, got {a.shape}")
@@ -325,8 +362,10 @@ def encode_rgba_lossless_host(image, keep_hidden=False, transform="green"):
             order = np.argsort(palette_key(colours))
             rank = np.empty(colours.size, dtype=np.uint8)
             rank[order] = np.arange(colours.size)
-            plane = alphaexact.encode_alpha_plane_host(rank[index.reshape(h, w)])
-            return build_rgba_palette(h, w, keep_hidden, colours[order], plane)
+            plane = rank[index.reshape(h, w)]
+            plane = (indexexact.encode_index_plane_host(plane, colours.size) if neighbour
+                     else alphaexact.encode_alpha_plane_host(plane))
+            return build_rgba_palette(h, w, keep_hidden, colours[order], plane, neighbour)
     adaptive = transform != "green"
     sym, ctx, vis = model_symbols(a, keep_hidden, adaptive)
     g = a[..., 1].astype(np.int64)
@@ -444,11 +483,11 @@ def _planes(sizes, dev):
     return flat, views, [(v.data_ptr(), h, w, w) for v, (h, w) in zip(views, sizes)]
 
 
-def _encode_palette(dev, sizes, entries, keep_hidden):
+def _encode_palette(dev, sizes, entries, keep_hidden, neighbour=False):
     """The three launches over a ragged batch (collect, order, map), one read-back of every
     image's overflow word, colour count and palette, then the plane coder over the index planes
     of the images that have a palette -> per image (palette uint32, RGAP blob), or None where
-    the image has more than 256 colours."""
+    the image has more than 256 colours.  ``neighbour``: the index coder and RGAI blobs."""
     B, stream = len(sizes), _lib.stream_ptr(dev)
     descs = anysize._upload_descs(entries, dev)
     flat, views, pentries = _planes(sizes, dev)
@@ -467,13 +506,18 @@ def _encode_palette(dev, sizes, entries, keep_hidden):
     ks = [k for k in range(B) if not host[k, 0]]
     out = [None] * B
     if ks:
-        blobs = alphaexact._encode(dev, [sizes[k] for k in ks], [pentries[k] for k in ks], 1)
+        if neighbour:
+            blobs = indexexact._encode(dev, [sizes[k] for k in ks], [pentries[k] for k in ks],
+                                       [int(host[k, 1]) for k in ks])
+        else:
+            blobs = alphaexact._encode(dev, [sizes[k] for k in ks], [pentries[k] for k in ks], 1)
         for k, blob in zip(ks, blobs):
             out[k] = (host[k, 2:2 + int(host[k, 1])].copy(), blob)
     return out
 
 
-def encode_rgba_lossless(images, keep_hidden=False, transform="green", device="cuda"):
+def encode_rgba_lossless(images, keep_hidden=False, transform="green", index_model="plane",
+                         device="cuda"):
     """images: a list of (h, w, 4) uint8 RGBA images of any sizes; GPU tensors are read in place,
     views into larger buffers included -> list[bytes], one RGAL file per image.  A hidden pixel
     (alpha 0) decodes to R = G = B = 0 and its colour bytes do not reach the file;
@@ -482,8 +526,12 @@ def encode_rgba_lossless(images, keep_hidden=False, transform="green", device="c
     where that codes shorter (version 2 files, smaller where the channels do not move together);
     "palette" writes an image of at most 256 distinct pixels as its palette and one plane of
     palette positions (version 3 files) and every other image as "adaptive" does.
+    ``index_model``, looked at under "palette" only: "plane" codes the positions with the alpha
+    plane coder; "neighbour" codes which neighbour a pixel equals (version 4 files, smaller on
+    flat and dithered images: DESIGN.md section 32).
     A file does not depend on the images coded with it."""
     transform = _transform(transform, "encode_rgba_lossless")
+    neighbour = transform == "palette" and _index_model(index_model, "encode_rgba_lossless")
     adaptive = transform != "green"
     dev = anysize._gpu_device(device)
     _lib.load()
@@ -493,9 +541,9 @@ def encode_rgba_lossless(images, keep_hidden=False, transform="green", device="c
     keep_hidden = bool(keep_hidden)
     files = [None] * len(sizes)
     if transform == "palette":
-        for k, found in enumerate(_encode_palette(dev, sizes, entries, keep_hidden)):
+        for k, found in enumerate(_encode_palette(dev, sizes, entries, keep_hidden, neighbour)):
             if found:
-                files[k] = build_rgba_palette(*sizes[k], keep_hidden, *found)
+                files[k] = build_rgba_palette(*sizes[k], keep_hidden, *found, neighbour)
     ks = [k for k, f in enumerate(files) if f is None]
     if ks:
         sizes, entries = [sizes[k] for k in ks], [entries[k] for k in ks]
@@ -530,11 +578,18 @@ def _decode_colour(parsed, entries, keep_hidden, dev, err, adaptive=False):
 
 
 def _decode_palette(parsed, entries, dev, err):
-    """Version 3 files onto the images ``entries`` describe: one plane-decoder launch into index
-    planes of their own, one unmap launch behind it on the same stream."""
+    """Version 3 and 4 files onto the images ``entries`` describe: one plane-decoder launch per
+    index model present into index planes of their own, one unmap launch behind them on the same
+    stream."""
     sizes = [(f["h"], f["w"]) for f in parsed]
     flat, views, pentries = _planes(sizes, dev)
-    alphaexact._decode([f["plane"] for f in parsed], pentries, 1, dev, err)
+    ks = [k for k, f in enumerate(parsed) if "index_model" not in f]
+    if ks:
+        alphaexact._decode([parsed[k]["plane"] for k in ks], [pentries[k] for k in ks], 1, dev,
+                           err)
+    ks = [k for k, f in enumerate(parsed) if f.get("index_model") == "neighbour"]
+    if ks:
+        indexexact._decode([parsed[k]["plane"] for k in ks], [pentries[k] for k in ks], dev, err)
     palettes = np.zeros((len(parsed), PALETTE_MAX), dtype=np.uint32)
     for k, f in enumerate(parsed):
         palettes[k, :f["palette"].size] = f["palette"]

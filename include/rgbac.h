@@ -1207,6 +1207,49 @@ int rgbac_color_palette_unmap(int batch, const rgbac_image_desc* descs,
                               const uint32_t* palettes, const int32_t* counts, int32_t* err,
                               void* stream);
 
+/* Palette index planes (csrc/index_exact.hip, rgbac/indexexact.py): the
+ * neighbour-match coder of the index plane of a version 4 RGAL file, an `RGAI` blob.  Blocks,
+ * class words, groups, block_base, the per-block arrays, the chunk format, the error word and
+ * the bounds discipline are rgbac_alpha_exact_*'s, and cls comes from rgbac_alpha_exact_classify
+ * with pixel_stride 1.  A pixel is coded as the rank of the neighbour it equals (W, N, NE, NW
+ * inside its block, duplicates dropped), or as an escape and a literal; the context is how the
+ * neighbours equal one another.  The model is fixed by the format: see csrc/index_exact.hip.
+ *   descs: DEVICE array of `batch` rgbac_image_desc, ptr = the plane's first byte (no alignment
+ *     asked), h, w, row_stride_bytes; the pixels of a row are 1 byte apart.
+ *   tables: DEVICE uint16[batch * RGBAC_INDEX_TABLE_U16], 4-byte aligned; per image the exclusive
+ *     sums (mod 2^16) of RGBAC_INDEX_CONTEXTS match tables of RGBAC_INDEX_SYMBOLS frequencies,
+ *     then of the 256 literal frequencies.
+ * rgbac_index_exact_tables: two launches.  partials: DEVICE uint32[batch *
+ *   RGBAC_INDEX_HIST_BLOCKS * RGBAC_INDEX_TABLE_U16], no initial contents needed, summed in index
+ *   order; freqs: DEVICE int32[batch * RGBAC_INDEX_TABLE_U16] in the tables' order (sum 2^16 per
+ *   table that is not empty), and `tables`.
+ * rgbac_index_exact_sizes / _encode / _decode: as rgbac_alpha_exact_sizes / _encode / _decode; a
+ *   chunk has between 2 and block pixels + 3 words.  _decode reports code 3 (corrupt) also for a
+ *   symbol of an empty table and for a rank that the pixel's candidates do not reach; a literal is
+ *   stored whatever its value. */
+#define RGBAC_INDEX_CONTEXTS 64
+#define RGBAC_INDEX_SYMBOLS 5
+#define RGBAC_INDEX_HIST_BLOCKS 16
+#define RGBAC_INDEX_TABLE_U16 576
+int rgbac_index_exact_tables(int batch, const rgbac_image_desc* descs, const int32_t* block_base,
+                             int total_blocks, const int32_t* cls, uint32_t* partials,
+                             int32_t* freqs, uint16_t* tables, void* stream);
+int rgbac_index_exact_sizes(int batch, const rgbac_image_desc* descs, int ngroups,
+                            const rgbac_alpha_group* groups, const int32_t* block_base,
+                            int total_blocks, const int32_t* cls, const uint16_t* tables,
+                            int32_t* counts, int32_t* err, void* stream);
+int rgbac_index_exact_encode(int batch, const rgbac_image_desc* descs, int ngroups,
+                             const rgbac_alpha_group* groups, const int32_t* block_base,
+                             int total_blocks, const int32_t* cls, const uint16_t* tables,
+                             const int32_t* counts, const int64_t* ends, uint32_t* payload,
+                             int64_t payload_words, int32_t* err, void* stream);
+int rgbac_index_exact_decode(int batch, const rgbac_image_desc* descs, int ngroups,
+                             const rgbac_alpha_group* groups, const int32_t* block_base,
+                             int total_blocks, const int32_t* cls, const uint16_t* tables,
+                             const int64_t* word_off, const int32_t* counts,
+                             const uint32_t* payload, int64_t payload_words, int32_t* err,
+                             void* stream);
+
 /* Near-lossless colour of packed RGBA (csrc/color_near.hip, rgbac/rgbanear.py, DESIGN.md section
  * 28): the colour half of an RGAN file.  Blocks, groups, visibility, contexts, tables, chunk
  * arrays and the class word layout are rgbac_color_exact_*'s; the planes are G, R, B, predicted

@@ -9,13 +9,15 @@ palette, as flat regions (a smooth field quantised to that many levels) and as a
 dither between neighbouring levels; the 16- and 256-colour ones have a transparent surround
 (a hard-edged disc).  Two are images 4 and 3 of tools/rgba_lossless_bench.py (opaque ramps;
 textured colour under a hard alpha): they have far more than 256 colours and show what the
-fall-back costs.  Reported per image: bytes as palette, adaptive and green files, the palette
-size, and zlib 9 of the index plane; per call: encode and decode of all ten as "palette" and as
-"adaptive", host clock plus a device synchronise, median (min to max) of ``--reps`` runs after
+fall-back costs.  Reported per image: bytes as palette (version 3), neighbour (version 4,
+index_model="neighbour"), adaptive and green files, the palette
+size, and zlib 9 of the index plane; per call: encode and decode of all ten as "palette", as
+"neighbour" and as "adaptive", host clock plus a device synchronise, median (min to max) of ``--reps`` runs after
 ``--warmup``, the two alternating inside each repetition.  Kernel times do not come from this
 process: run it once under ``rocprofv3 --kernel-trace -f csv -d DIR -- python
 tools/rgba_palette_bench.py --no-headline --out /dev/null`` and then with ``--kernel-trace DIR``,
-which adds the median duration of the palette kernels and of the plane coder's.  Unless
+which adds the median duration of the palette kernels, of the plane coder's and of the index
+coder's.  Unless
 --no-headline: ``bench.py --gpus 1 --steps 20 --warmup 5`` in a fresh process.  GPU only."""
 import argparse
 import csv
@@ -61,12 +63,12 @@ def palette_images(dev):
 
 def kernel_medians(trace_dir):
     """rocprofv3's kernel trace CSVs under ``trace_dir`` -> {kernel: {"median_us", "calls"}} for
-    the kernels of color_palette.hip and alpha_exact.hip."""
+    the kernels of color_palette.hip, alpha_exact.hip and index_exact.hip."""
     spans = {}
     for path in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
         with open(path, newline="") as fh:
             for row in csv.DictReader(fh):
-                found = re.search(r"::((?:palette|alpha)_\w+?)_kernel(<\w+>)?\(", row["Kernel_Name"])
+                found = re.search(r"::((?:palette|alpha|index)_\w+?)_kernel(<\w+>)?\(", row["Kernel_Name"])
                 if found:
                     short = found.group(1) + {"<true>": "<encode>", "<false>": "<sizes>",
                                               None: ""}[found.group(2)]
@@ -98,21 +100,27 @@ def main():
         torch.cuda.synchronize()
         return r, (time.perf_counter() - t0) * 1e3
 
-    modes = ("adaptive", "palette")
+    modes = ("adaptive", "palette", "neighbour")
+
+    def encode(t):
+        if t == "neighbour":
+            return rl.encode_rgba_lossless(ims, transform="palette", index_model="neighbour")
+        return rl.encode_rgba_lossless(ims, transform=t)
+
     coded = {"green": rl.encode_rgba_lossless(ims)}
     want = [im.clone() for im in ims]
     for im in want:
         im[im[..., 3] == 0] = 0
     for t in modes:
         for _ in range(args.warmup):
-            coded[t] = rl.encode_rgba_lossless(ims, transform=t)
+            coded[t] = encode(t)
             out = rl.decode_rgba_lossless(coded[t])
         if not all(torch.equal(a, b) for a, b in zip(out, want)):
             raise SystemExit(f"rgba_palette_bench: the {t} round trip is not exact")
     te, td = {t: [] for t in modes}, {t: [] for t in modes}
     for _ in range(args.reps):
         for t in modes:
-            c, ms = timed(lambda: rl.encode_rgba_lossless(ims, transform=t))
+            c, ms = timed(lambda: encode(t))
             te[t].append(ms)
             td[t].append(timed(lambda: rl.decode_rgba_lossless(c))[1])
     parsed = [rl.parse_rgba_lossless(b) for b in coded["palette"]]
@@ -133,6 +141,8 @@ def main():
            "versions": [int(b[4]) for b in coded["palette"]],
            "palette_colours": [int(f["palette"].size) if "palette" in f else None for f in parsed],
            "palette_bytes": [len(b) for b in coded["palette"]],
+           "neighbour_versions": [int(b[4]) for b in coded["neighbour"]],
+           "neighbour_bytes": [len(b) for b in coded["neighbour"]],
            "adaptive_bytes": [len(b) for b in coded["adaptive"]],
            "green_bytes": [len(b) for b in coded["green"]],
            "zlib9_index_plane_bytes": index,
